@@ -18,6 +18,13 @@ process group is used only for the barrier and the max-over-ranks time.
 `--gpus N` without a launcher's WORLD_SIZE starts N ranks itself
 (torch.distributed.run, before anything touches the GPU).
 
+A plain run sets up, warms up, times `--steps` steps and prints.  `--full`
+adds, after the timed steps, everything beside the headline figure: the
+correctness gate against the oracle, the CPU baselines, the PCIe-inclusive
+and per-call legs and the other BASELINE configs.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (float32, a fixed
+seeded sample), so two builds can be compared output for output.
+
 `--ref-cases` instead mirrors rust/benches/ec.rs (matrix inversion, rs-encode
 of 6 x 16 MiB, decode with 1/2/3 data slices missing) with the CPU port timed
 in the same run.
@@ -62,13 +69,13 @@ def parse(argv=None):
     ap.add_argument("--stripes", type=int, default=1024, help="stripes per GPU (weak scaling)")
     ap.add_argument("--global-stripes", type=int, default=0,
                     help="split this many stripes across the ranks instead (strong scaling)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: CPU baseline budget (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "0") or 0),
                     help="also time the oracle stripe-parallel on T threads (default $OMP_NUM_THREADS: the "
                          "box's CPU share; 0/1 = single-threaded only)")
     ap.add_argument("--host-path", type=int, default=-1,
-                    help="also measure the PCIe-inclusive paths (pinned pipelines and the per-call drop-in): "
-                         "1 = yes, 0 = no, -1 = default (yes at N=1)")
+                    help="with --full: also measure the PCIe-inclusive paths (pinned pipelines and the per-call "
+                         "drop-in): 1 = yes, 0 = no, -1 = default (yes at N=1)")
     ap.add_argument("--traffic", default=TRAFFIC_FILE)
     ap.add_argument("--tune", default="", help="key=value,... passed to hec_tune_set (measurement)")
     ap.add_argument("--encode-only", action="store_true")
@@ -88,13 +95,23 @@ def parse(argv=None):
                     help="launcher / rank / reduction plumbing only: no GPU, no engine, value null (CPU tests)")
     ap.add_argument("--spinup", type=float, default=0.5, help="untimed seconds of steps before warmup")
     ap.add_argument("--extra-configs", type=int, default=-1,
-                    help="also time the other multi-GPU BASELINE configs (RS(10,4) 1 MiB x 2048 and RS(6,3) "
-                         "64 KiB x 65536, both split over the ranks): 1 = yes, 0 = no, -1 = default (yes for the "
-                         "default RS(6,3) run)")
+                    help="with --full: also time the other multi-GPU BASELINE configs (RS(10,4) 1 MiB x 2048 and "
+                         "RS(6,3) 64 KiB x 65536, both split over the ranks): 1 = yes, 0 = no, -1 = default (yes for "
+                         "the default RS(6,3) run)")
     ap.add_argument("--rows-call-host", action="store_true",
                     help="internal: the host-routine side of host_path.rows_call (child process, no GPU)")
     ap.add_argument("--verify", default="full", choices=["full", "sample"],
-                    help="post-timing correctness gate: every stripe against the C oracle (full) or stripe 0")
+                    help="with --full, the post-timing correctness gate: every stripe against the C oracle (full) "
+                         "or stripe 0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the correctness "
+                         "gate against the oracle, the CPU baselines, the PCIe-inclusive and per-call legs and "
+                         "the other BASELINE configs (--verify, --cpu-seconds, --host-path, --extra-configs "
+                         "choose among them); without it the run sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last step computed (parity, and the rebuilt "
+                         "cells unless --encode-only) to DIR/<name>.npy as float32: a fixed, seeded sample of "
+                         "each output (at most 4 Mi elements each), the same indices for the same arguments")
     return ap.parse_args(argv)
 
 
@@ -902,19 +919,32 @@ def main():
     elapsed = max_over_ranks(t1 - t0, dev)
     log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.3f} ms/step")
 
-    # correctness gate (after the timed region): decode reconstructs the
-    # erased shards of every stripe (on the device), and every stripe's parity
-    # and rebuilt cells match the C oracle bit for bit (stripe-parallel on the
-    # host's CPU share; --verify sample: stripe 0 only)
-    if not args.encode_only and not mixed:
-        assert torch.equal(rec, data[:, :m]), "decode != original"
+    lost = None
     if not args.encode_only and mixed:
         lost = torch.tensor([[not (mk >> i) & 1 for i in range(k)] for mk in masks], device=dev)
-        assert bool(((rec == data) | ~lost[:, :, None]).all()), "mixed decode != original"
-    import ec_oracle
-    clib = ec_oracle.load_c_oracle()
-    verified = verify_batch(args, ec_oracle, clib, data, parity, None if (args.encode_only or mixed) else rec, k, m)
-    log(f"verified: {verified}")
+    dumped = None
+    if args.dump_outputs:
+        outs = {"parity": (parity, None)}
+        if not args.encode_only:
+            outs["rebuilt"] = (rec, lost)  # mixed: only the lost cells are written
+        dumped = dump_outputs(args.dump_outputs, outs, rank, world)
+        log(f"outputs written to {args.dump_outputs}")
+
+    # --full: correctness gate (after the timed region): decode reconstructs
+    # the erased shards of every stripe (on the device), and every stripe's
+    # parity and rebuilt cells match the C oracle bit for bit (stripe-parallel
+    # on the host's CPU share; --verify sample: stripe 0 only)
+    verified = "not checked (a plain run; --full checks every stripe against the oracle)"
+    if args.full:
+        if not args.encode_only and not mixed:
+            assert torch.equal(rec, data[:, :m]), "decode != original"
+        if not args.encode_only and mixed:
+            assert bool(((rec == data) | ~lost[:, :, None]).all()), "mixed decode != original"
+        import ec_oracle
+        clib = ec_oracle.load_c_oracle()
+        verified = verify_batch(args, ec_oracle, clib, data, parity, None if (args.encode_only or mixed) else rec,
+                                k, m)
+        log(f"verified: {verified}")
 
 
     enc_ms = [evs[i][0].elapsed_time(evs[i][1]) for i in range(args.steps)]
@@ -1001,7 +1031,11 @@ def main():
         result["crc32c"] = crc_leg(args, H, coder, data, parity, rec, dp, ds, pp, ps, rp, rs, shard_ptrs, miss,
                                    decode, dev, stream, mixed)
 
-    host_path = args.host_path if args.host_path >= 0 else int(world == 1)
+    if dumped is not None:
+        result["outputs_dumped"] = dumped
+
+    # everything below is beside the headline figure: --full only
+    host_path = args.full and (args.host_path if args.host_path >= 0 else int(world == 1))
     if host_path and rank == 0 and not mixed:
         result["host_path"] = pinned_leg(coder, data, parity, k, m, cell, S, torch)
         result["host_path"]["per_call"] = per_call_leg(H, k, m, cell, 64, clib)
@@ -1011,7 +1045,7 @@ def main():
         result["host_path"]["rows_call"] = rows_call_leg(H, k, m, cell, coder, torch)
         log("writer / reader call shapes")
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         log("cpu baseline")
         result["cpu_baseline"] = cpu_baseline(k, m, cell, args.cpu_seconds, 1)
         if args.cpu_threads > 1:
@@ -1030,9 +1064,9 @@ def main():
     elif rank == 0:
         result["cpu_baseline"] = None
 
-    extra = args.extra_configs if args.extra_configs >= 0 else int(
+    extra = args.full and (args.extra_configs if args.extra_configs >= 0 else int(
         (k, m, cell, args.codec, args.decode_mode) == (6, 3, 1 << 20, "rs", "uniform") and not args.global_stripes
-        and not args.encode_only and not args.tune)
+        and not args.encode_only and not args.tune))
     if extra:
         del data, parity, rec
         torch.cuda.empty_cache()
@@ -1047,6 +1081,45 @@ def main():
     coder.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per output: 16 MiB as float32, two outputs stay far below 64 MB
+DUMP_SEED = 0xD0_0D5EED
+
+
+def dump_outputs(path, outs, rank, world):
+    """--dump-outputs: every output of the last timed step as
+    DIR/<name>.npy (float32; `<name>_rank<r>` on more than one rank).  An
+    output of more than DUMP_MAX_ELEMS bytes is sampled: DUMP_MAX_ELEMS flat
+    positions, sorted, drawn without the data from a generator seeded by
+    DUMP_SEED and the output's shape, so two runs with the same arguments
+    write the same positions.  `outs` maps name -> (uint8 device tensor,
+    mask or None); a mask [S, shards] marks the cells the step wrote, every
+    other position is written as 0."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for idx, (name, (t, mask)) in enumerate(outs.items()):
+        n = t.numel()
+        flat = t.reshape(-1)
+        pos = None
+        if n > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([DUMP_SEED, idx, *t.shape])
+            pos = torch.from_numpy(np.sort(rng.integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))).to(t.device)
+            flat = flat[pos]
+        if mask is not None:
+            cell = t.shape[-1]
+            cells = (pos if pos is not None else torch.arange(n, device=t.device)) // cell
+            flat = torch.where(mask.reshape(-1)[cells], flat, torch.zeros_like(flat))
+        arr = flat.to(torch.float32).cpu().numpy()
+        fname = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(path, fname + ".npy"), arr)
+        info[name] = {"file": fname + ".npy", "dtype": "float32", "elements": int(arr.size),
+                      "of": [int(x) for x in t.shape],
+                      "sample": "whole" if pos is None else f"{DUMP_MAX_ELEMS} sorted flat positions, seed "
+                                                            f"[{DUMP_SEED:#x}, {idx}, shape]"}
+    return info
 
 
 def verify_batch(args, ec_oracle, clib, data, parity, rec, k, m):

@@ -15,7 +15,7 @@
 set -o pipefail
 o=${1:-gpurun_out/ab_jit}; shift
 mkdir -p "$o"; export TMPDIR=/tmp
-B="--crc --corrupt none --steps 10 --warmup 3 --extra-configs 0 --cpu-seconds 0 --host-path 0 --verify sample $*"
+B="--crc --corrupt none --steps 10 --warmup 3 --extra-configs 0 --full --cpu-seconds 0 --host-path 0 --verify sample $*"
 for rep in $(seq 1 ${AB_REPS:-2}); do
   for v in ${AB_VARIANTS:-aot jit8 jit4}; do
     case $v in

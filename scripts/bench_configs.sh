@@ -3,11 +3,12 @@
 set -o pipefail
 out=${1:-gpurun_out/configs.jsonl}
 : > "$out"
+log="$(dirname "$out")/_cfg.log"
 run() {
     local name="$1"; shift
-    timeout -k 10 300 python3 bench.py "$@" > gpurun_out/_cfg.log 2>&1 || { echo "FAILED $name"; tail -20 gpurun_out/_cfg.log; exit 1; }
-    echo "{\"config\": \"$name\", \"args\": \"$*\", \"result\": $(tail -1 gpurun_out/_cfg.log)}" >> "$out"
-    tail -1 gpurun_out/_cfg.log | python3 -c 'import json,sys; d=json.load(sys.stdin); print("'"$name"'", d["value"], d["unit"], d["roofline"]["achieved"], d["roofline"]["frac"], (d.get("cpu_baseline") or {}).get("value"))'
+    timeout -k 10 300 python3 bench.py --full "$@" > "$log" 2>&1 || { echo "FAILED $name"; tail -20 "$log"; exit 1; }
+    echo "{\"config\": \"$name\", \"args\": \"$*\", \"result\": $(tail -1 "$log")}" >> "$out"
+    tail -1 "$log" | python3 -c 'import json,sys; d=json.load(sys.stdin); print("'"$name"'", d["value"], d["unit"], d["roofline"]["achieved"], d["roofline"]["frac"], (d.get("cpu_baseline") or {}).get("value"))'
 }
 run "RS(3,2) 1MiB x1024 enc+dec" --k 3 --m 2 --stripes 1024 --cpu-seconds 10 --host-path 0
 run "RS(6,3) 1MiB x1024 encode" --encode-only --cpu-seconds 0 --host-path 0

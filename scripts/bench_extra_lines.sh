@@ -6,7 +6,7 @@
 set -o pipefail
 out=${1:-gpurun_out/extra}
 mkdir -p $out
-C="--cpu-seconds 0 --host-path 0"
+C="--full --cpu-seconds 0 --host-path 0"
 timeout -k 10 200 python3 -u bench.py --decode-mode mixed $C > $out/mixed63.log 2>&1 || exit 1
 timeout -k 10 200 python3 -u bench.py --k 10 --m 4 --stripes 512 --decode-mode mixed $C > $out/mixed104.log 2>&1 || exit 2
 timeout -k 10 200 python3 -u bench.py --k 10 --m 4 --stripes 256 --decode-mode mixed $C > $out/mixed104x256.log 2>&1 || exit 3

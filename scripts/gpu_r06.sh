@@ -22,7 +22,7 @@ tail -3 "$out/tests.txt"
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1 || exit 2
 tail -1 "$out/smoke.txt"
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python3 -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 3; }
+  timeout -k 10 400 python3 -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 3; }
   cut -c1-500 "$out/bench.json"
 fi
 echo "gpu_r06 ok"

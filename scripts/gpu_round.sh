@@ -14,7 +14,7 @@ rc=$?
 tail -4 "$out/gpu_tests.txt"
 [ $rc -le 1 ] || { echo "pytest rc=$rc: stop"; exit 1; }
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.txt" 2>&1 || exit 2
-timeout -k 10 600 python3 -u bench.py > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 3; }
+timeout -k 10 600 python3 -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 3; }
 tail -c 600 "$out/bench.json"
 if [ $# -gt 0 ]; then
   timeout -k 10 1500 python3 -u scripts/profile_configs.py "$out/prof" "$@" > "$out/prof.log" 2>&1 || { tail -20 "$out/prof.log"; exit 4; }

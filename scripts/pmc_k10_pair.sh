@@ -9,7 +9,7 @@ set -o pipefail
 out=${1:-gpurun_out/pmc_k10}
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="--encode-only --steps 10 --warmup 3 --verify sample --extra-configs 0 --cpu-seconds 0 --host-path 0 --spinup 0.3"
+B="--encode-only --steps 10 --warmup 3 --verify sample --extra-configs 0 --full --cpu-seconds 0 --host-path 0 --spinup 0.3"
 i=0
 for cfg in "--k 6 --m 3 --stripes 1024" "--k 10 --m 4 --stripes 256" "--k 10 --m 4 --stripes 1024"; do
   i=$((i+1))

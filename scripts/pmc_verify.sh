@@ -7,7 +7,7 @@ set -o pipefail
 out=${1:-gpurun_out/pmc_verify}
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="--crc --corrupt none --steps 3 --warmup 1 --extra-configs 0 --cpu-seconds 0 --host-path 0 --verify sample --spinup 0.1"
+B="--crc --corrupt none --steps 3 --warmup 1 --extra-configs 0 --full --cpu-seconds 0 --host-path 0 --verify sample --spinup 0.1"
 i=0
 for v in 0 async; do
   for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_LDS GRBM_GUI_ACTIVE" \

@@ -6,7 +6,7 @@ set -o pipefail
 out=${1:-gpurun_out/pmc_waves}
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="--encode-only --steps 5 --warmup 2 --verify sample --extra-configs 0 --cpu-seconds 0 --host-path 0 --spinup 0.2"
+B="--encode-only --steps 5 --warmup 2 --verify sample --extra-configs 0 --full --cpu-seconds 0 --host-path 0 --spinup 0.2"
 i=0
 for tune in 3=1 3=2; do
   for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_LDS GRBM_GUI_ACTIVE" \

@@ -1,6 +1,6 @@
 """The bench line's dominant kernel in a rocprofv3 kernel trace of the SAME
 default command (scripts/gpu_r06final.sh: `rocprofv3 --kernel-trace --stats
--- python3 bench.py`): the trace's averaged stats mix every leg that runs the
+-- python3 bench.py --full`): the trace's averaged stats mix every leg that runs the
 same instantiation (spin-up, per-call rows of 16 B .. 1 MiB, the extra
 configs), so this picks the timed region itself -- the last 2 x steps
 dispatches of the first contiguous run of full-batch launches (no other

@@ -6,7 +6,7 @@
 set -o pipefail
 out=${1:-gpurun_out/k10s}
 mkdir -p $out
-C="--cpu-seconds 0 --host-path 0 --k 10 --m 4 --global-stripes 2048 --steps 10 --warmup 3"
+C="--full --cpu-seconds 0 --host-path 0 --k 10 --m 4 --global-stripes 2048 --steps 10 --warmup 3"
 for r in 1 2; do
   for t in "" "8=1" "8=2" "8=8" "8=16" "3=4" "3=16" "1=1" "1=4"; do
     tag="t${t:-def}_r$r"

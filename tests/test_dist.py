@@ -127,8 +127,9 @@ def test_bench_gpus_flag_spawns_ranks(args, want_S, want_global, scaling):
     assert d["config"]["global_stripes"] == want_global
     assert d["config"]["stripes_summed_over_ranks"] == want_global
     assert d["config"]["stripes_per_gpu"] == want_S  # rank 0's share
-    # the other multi-GPU BASELINE configs are timed by the same invocation,
-    # each split over the ranks (bench.py --extra-configs)
+    # the other multi-GPU BASELINE configs, which a `--full` run times in the
+    # same invocation, each split over the ranks (bench.py --extra-configs):
+    # the dry run lists their split
     ex = d["extra_configs"]
     assert set(ex) == {"rs63_1MiB_x1024_strong", "rs104_1MiB_x2048", "rs63_64KiB_x65536"}
     assert ex["rs63_1MiB_x1024_strong"]["stripes_per_gpu_rank0"] == 512
