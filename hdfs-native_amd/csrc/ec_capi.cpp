@@ -64,6 +64,16 @@ struct DecodePlan {
     std::vector<uint8_t> matrix;    // e x k
     std::vector<uint32_t> perm;     // e x k x 8: the matrix's v_perm product tables (mixed-decode plan blobs)
     std::vector<uint64_t> aff;      // e x k: the matrix's host affine qwords (small-row host path)
+    // Reconstruction (hec_reconstruct*): every missing unit, parity included.
+    // The fields above stay what the decode calls have always seen; these
+    // carry one row per lost unit, and a call's `want` selects among them.
+    int rec_status = HEC_OK;            // NOT_ENOUGH_SHARDS / SINGULAR apply once a unit is wanted
+    std::vector<size_t> rec_survivors;  // k: the first k present units (also when only parity is lost)
+    std::vector<size_t> lost;           // every missing unit, ascending (data units first)
+    std::vector<uint8_t> rec_matrix;    // lost x k: data unit t -> row t of the inverse,
+                                        // parity unit k+j -> enc[k+j] . inverse
+    std::vector<uint32_t> rec_perm;     // lost x k x 8: v_perm product tables of rec_matrix
+    std::vector<uint64_t> rec_aff;      // lost x k: host affine qwords of rec_matrix
 };
 
 // Restores the caller's current HIP device on scope exit.
@@ -159,33 +169,73 @@ DecodePlan compute_plan(size_t k, size_t m, const uint8_t* present, const std::v
     DecodePlan p;
     std::vector<size_t> valid;
     for (size_t i = 0; i < k + m; i++) {
-        if (present[i])
+        if (present[i]) {
             valid.push_back(i);
-        else if (i < k)
-            p.missing.push_back(i);  // gf256.rs:96-97: only data indices
+        } else {
+            p.lost.push_back(i);
+            if (i < k) p.missing.push_back(i);  // gf256.rs:96-97: only data indices
+        }
+    }
+    // inverse(select_rows(enc, first k present)), shared by both sides
+    std::vector<uint8_t> sub;
+    if (!p.lost.empty()) {
+        if (valid.size() < k) {
+            p.rec_status = HEC_ERR_NOT_ENOUGH_SHARDS;
+        } else {
+            p.rec_survivors.assign(valid.begin(), valid.begin() + k);
+            sub.resize(k * k);
+            for (size_t r = 0; r < k; r++) std::memcpy(&sub[r * k], &enc[p.rec_survivors[r] * k], k);  // select_rows
+            if (!hec::invert(sub.data(), k)) {
+                p.rec_status = HEC_ERR_SINGULAR;
+            } else {
+                p.rec_matrix.assign(p.lost.size() * k, 0);
+                for (size_t r = 0; r < p.lost.size(); r++) {
+                    const size_t t = p.lost[r];
+                    if (t < k) {
+                        std::memcpy(&p.rec_matrix[r * k], &sub[t * k], k);
+                        continue;
+                    }
+                    for (size_t i = 0; i < k; i++) {  // enc[t] . inverse
+                        uint8_t v = 0;
+                        for (size_t x = 0; x < k; x++) v ^= hec::gf_mul(enc[t * k + x], sub[x * k + i]);
+                        p.rec_matrix[r * k + i] = v;
+                    }
+                }
+                p.rec_perm.resize(p.rec_matrix.size() * 8);
+                for (size_t x = 0; x < p.rec_matrix.size(); x++) {
+                    const auto w = hec::perm_table_words(p.rec_matrix[x]);
+                    std::memcpy(&p.rec_perm[x * 8], w.data(), sizeof(uint32_t) * 8);
+                }
+                p.rec_aff = hec::host::affine_matrices(p.rec_matrix.data(), p.rec_matrix.size());
+            }
+        }
     }
     if (p.missing.empty()) return p;  // gf256.rs:102-105
     if (valid.size() < k) {           // gf256.rs:107-111
         p.status = HEC_ERR_NOT_ENOUGH_SHARDS;
         return p;
     }
-    p.survivors.assign(valid.begin(), valid.begin() + k);  // first k present, ascending
-    std::vector<uint8_t> sub(k * k);
-    for (size_t r = 0; r < k; r++) std::memcpy(&sub[r * k], &enc[p.survivors[r] * k], k);  // select_rows
-    if (!hec::invert(sub.data(), k)) {
-        p.status = HEC_ERR_SINGULAR;
+    p.survivors = p.rec_survivors;  // first k present, ascending
+    if (p.rec_status != HEC_OK) {
+        p.status = p.rec_status;  // singular
         return p;
     }
-    p.matrix.resize(p.missing.size() * k);
-    for (size_t r = 0; r < p.missing.size(); r++)  // select_rows(invalid), ascending
-        std::memcpy(&p.matrix[r * k], &sub[p.missing[r] * k], k);
-    p.perm.resize(p.matrix.size() * 8);
-    for (size_t x = 0; x < p.matrix.size(); x++) {
-        const auto w = hec::perm_table_words(p.matrix[x]);
-        std::memcpy(&p.perm[x * 8], w.data(), sizeof(uint32_t) * 8);
-    }
-    p.aff = hec::host::affine_matrices(p.matrix.data(), p.matrix.size());
+    // select_rows(invalid), ascending: `lost` lists the data units first, so
+    // the decode's rows, tables and qwords are the first e of rec_*
+    const size_t ek = p.missing.size() * k;
+    p.matrix.assign(p.rec_matrix.begin(), p.rec_matrix.begin() + ek);
+    p.perm.assign(p.rec_perm.begin(), p.rec_perm.begin() + ek * 8);
+    p.aff.assign(p.rec_aff.begin(), p.rec_aff.begin() + ek);
     return p;
+}
+
+// The rows of a plan a reconstruction call asks for: positions in p.lost of
+// the units in `want_mask` (every lost unit when the caller passed no want).
+std::vector<size_t> target_rows(const DecodePlan& p, bool have_want, uint64_t want_mask) {
+    std::vector<size_t> rows;
+    for (size_t r = 0; r < p.lost.size(); r++)
+        if (!have_want || ((want_mask >> p.lost[r]) & 1)) rows.push_back(r);
+    return rows;
 }
 
 using PlanRef = std::shared_ptr<const DecodePlan>;
@@ -459,6 +509,40 @@ int hec_decode_plan(size_t data_units, size_t parity_units, const uint8_t* prese
         if (missing) std::copy(p.missing.begin(), p.missing.end(), missing);
         if (matrix) std::copy(p.matrix.begin(), p.matrix.end(), matrix);
         return HEC_OK;
+    });
+}
+
+int hec_reconstruct_plan(const char* codec, size_t data_units, size_t parity_units, const uint8_t* present,
+                         const uint8_t* want, size_t* n_targets, size_t* survivors, size_t* targets,
+                         uint8_t* matrix) {
+    if (!present || !n_targets || data_units == 0 || parity_units == 0 || data_units + parity_units > 64)
+        return HEC_ERR_INVALID_ARG;
+    const std::string name = codec ? codec : "rs";
+    if (name != "rs" && name != "xor" && name != "rs-legacy") return HEC_ERR_UNSUPPORTED_CODEC;
+    if (name == "xor" && parity_units != 1) return HEC_ERR_INVALID_ARG;
+    const size_t k = data_units, n = data_units + parity_units;
+    uint64_t want_mask = 0;
+    if (want)
+        for (size_t i = 0; i < n; i++) {
+            if (!want[i]) continue;
+            if (present[i]) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+            want_mask |= uint64_t(1) << i;
+        }
+    return guarded([&] {
+        const std::vector<uint8_t> enc = name == "xor"         ? hec::gen_xor_matrix(data_units)
+                                         : name == "rs-legacy" ? hec::gen_rs_legacy_matrix(data_units, parity_units)
+                                                               : hec::gen_rs_matrix(data_units, parity_units);
+        const DecodePlan p = compute_plan(data_units, parity_units, present, enc);
+        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
+        *n_targets = rows.size();
+        if (rows.empty()) return int(HEC_OK);
+        if (p.rec_status != HEC_OK) return p.rec_status;
+        if (survivors) std::copy(p.rec_survivors.begin(), p.rec_survivors.end(), survivors);
+        for (size_t t = 0; t < rows.size(); t++) {
+            if (targets) targets[t] = p.lost[rows[t]];
+            if (matrix) std::memcpy(matrix + t * k, &p.rec_matrix[rows[t] * k], k);
+        }
+        return int(HEC_OK);
     });
 }
 
@@ -977,6 +1061,353 @@ int hec_decode_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, cons
     return guarded([&] {
         return mixed_decode_impl(c, d_shards, shard_strides, d_out, out_strides, present, cell_len, stripes,
                                  d_workspace, workspace_bytes, hip_stream);
+    });
+}
+
+// ---- reconstruction: any lost unit, parity included ------------------------
+// Hadoop's RSRawDecoder.decode(inputs, erasedIndexes, outputs): what block-
+// group repair needs and the reference's reader (gf256.rs:96-97) never does.
+// The plan of a presence mask carries a row per lost unit (DecodePlan::rec_*);
+// `want` picks the rows of one call.
+
+namespace {
+
+// One call's targets out of a cached plan: the units, and their rows / host
+// affine qwords gathered contiguously (the plan's own arrays when every lost
+// unit is wanted).
+struct Targets {
+    std::vector<size_t> units;
+    const uint8_t* matrix = nullptr;
+    const uint64_t* aff = nullptr;
+    std::vector<uint8_t> matrix_store;
+    std::vector<uint64_t> aff_store;
+};
+
+void gather_targets(const DecodePlan& p, size_t k, const std::vector<size_t>& rows, Targets& t) {
+    for (size_t r : rows) t.units.push_back(p.lost[r]);
+    if (rows.size() == p.lost.size()) {
+        t.matrix = p.rec_matrix.data();
+        t.aff = p.rec_aff.data();
+        return;
+    }
+    for (size_t r : rows) {
+        t.matrix_store.insert(t.matrix_store.end(), p.rec_matrix.begin() + r * k, p.rec_matrix.begin() + (r + 1) * k);
+        t.aff_store.insert(t.aff_store.end(), p.rec_aff.begin() + r * k, p.rec_aff.begin() + (r + 1) * k);
+    }
+    t.matrix = t.matrix_store.data();
+    t.aff = t.aff_store.data();
+}
+
+// want[k+m] (NULL = every missing unit) as a bit mask; false when a wanted
+// unit is present.
+bool want_bits(const uint8_t* want, const uint8_t* present, size_t n, uint64_t* mask) {
+    *mask = 0;
+    if (!want) return true;
+    for (size_t i = 0; i < n; i++) {
+        if (!want[i]) continue;
+        if (present[i]) return false;
+        *mask |= uint64_t(1) << i;
+    }
+    return true;
+}
+
+// pairs of (presence mask, non-empty wanted subset of its <= m lost units):
+// sum_{j=1..m} C(k+m, j) (2^j - 1), capped by the stripe count
+size_t max_recon_plans(size_t k, size_t m, size_t stripes) {
+    double total = 0, c = 1, pw = 1;
+    for (size_t j = 1; j <= m; j++) {
+        c = c * double(k + m - j + 1) / double(j);
+        pw *= 2;
+        total += c * (pw - 1);
+        if (total >= double(stripes)) return stripes;
+    }
+    return std::min(stripes, size_t(total));
+}
+
+// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters]
+// (hec::ReconArgs; the layout of the mixed decode's workspace).  Only the
+// fused kernel reads it, and only when offsets + blob fit its resident LDS:
+// the blob term is capped there (a larger batch runs per run of stripes and
+// never touches the workspace).
+size_t recon_workspace(size_t k, size_t m, size_t stripes) {
+    const size_t p = max_recon_plans(k, m, stripes);
+    const size_t blob = std::min(p * (sizeof(hec::DevPlanHeader) + m * k * sizeof(hec::PermTable)),
+                                 size_t(hec::kReconResidentMax));
+    return align_up(align_up(stripes * sizeof(uint32_t)) + blob) + hec::kMixedQueueBytes;
+}
+
+}  // namespace
+
+int hec_reconstruct(hec_coder_t* c, const uint8_t* const* shards, size_t shard_len, const uint8_t* want,
+                    uint8_t* const* out) {
+    if (!c || !shards || shard_len == 0) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t k = c->k, n = c->k + c->m;
+        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+        for (size_t i = 0; i < n; i++) present[i] = shards[i] != nullptr;
+        uint64_t want_mask;
+        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
+        const PlanRef p_ref = cached_plan(c, present);
+        const DecodePlan& p = *p_ref;
+        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
+        if (rows.empty()) return HEC_OK;
+        if (p.rec_status != HEC_OK) return p.rec_status;
+        if (!out) return HEC_ERR_INVALID_ARG;
+        Targets t;
+        gather_targets(p, k, rows, t);
+        for (size_t u : t.units)
+            if (!out[u]) return HEC_ERR_INVALID_ARG;
+        const uint8_t* in[HEC_MAX_DATA_UNITS];
+        uint8_t* dst[HEC_MAX_PARITY_UNITS];
+        for (size_t r = 0; r < k; r++) in[r] = shards[p.rec_survivors[r]];
+        for (size_t r = 0; r < t.units.size(); r++) dst[r] = out[t.units[r]];
+        return code_row(c, t.matrix, t.aff, in, k, dst, t.units.size(), shard_len);
+    });
+}
+
+int hec_reconstruct_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                           uint8_t* const* d_out, const size_t* out_strides, const uint8_t* want, size_t cell_len,
+                           size_t stripes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_device");
+    if (!c || !d_shards || !shard_strides || cell_len == 0) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t k = c->k, n = c->k + c->m;
+        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+        for (size_t i = 0; i < n; i++) present[i] = d_shards[i] != nullptr;
+        uint64_t want_mask;
+        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
+        const PlanRef p_ref = cached_plan(c, present);
+        const DecodePlan& p = *p_ref;
+        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
+        if (rows.empty()) return HEC_OK;
+        if (p.rec_status != HEC_OK) return p.rec_status;
+        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
+        Targets t;
+        gather_targets(p, k, rows, t);
+        for (size_t u : t.units)
+            if (!d_out[u]) return HEC_ERR_INVALID_ARG;
+        const uint8_t* in[HEC_MAX_DATA_UNITS];
+        size_t ist[HEC_MAX_DATA_UNITS];
+        uint8_t* out[HEC_MAX_PARITY_UNITS];
+        size_t ost[HEC_MAX_PARITY_UNITS];
+        for (size_t r = 0; r < k; r++) {
+            in[r] = d_shards[p.rec_survivors[r]];
+            ist[r] = shard_strides[p.rec_survivors[r]];
+        }
+        for (size_t r = 0; r < t.units.size(); r++) {
+            out[r] = d_out[t.units[r]];
+            ost[r] = out_strides[t.units[r]];
+        }
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        // all m parity units of an intact data set: the rows are the coding
+        // matrix's parity rows, and launch_gf_matmul (rs_parity_matrix) picks
+        // the encode kernels for them -- hec_encode_device by another name
+        return matmul_batch(c->device, t.matrix, t.units.size(), k, in, ist, out, ost, cell_len, stripes,
+                            static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+size_t hec_reconstruct_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return recon_workspace(c->k, c->m, stripes);
+}
+
+namespace {
+
+// One distinct (presence mask, wanted units) pair of a mixed batch.
+struct ReconPlan {
+    PlanRef plan;
+    std::vector<size_t> rows;  // positions in plan->lost
+};
+
+int mixed_reconstruct_impl(hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                           uint8_t* const* d_out, const size_t* out_strides, const uint64_t* present,
+                           const uint64_t* want, size_t cell_len, size_t stripes, void* d_workspace,
+                           size_t workspace_bytes, void* hip_stream) {
+    const size_t k = c->k, m = c->m, n = k + m;
+    const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
+    // 1. plan per distinct (present, want) pair (host); fail before launching anything
+    std::map<std::pair<uint64_t, uint64_t>, uint16_t> ids;
+    std::vector<ReconPlan> plans;
+    std::vector<uint16_t> stripe_plan(stripes);
+    size_t max_e = 0;
+    uint64_t target_units = 0;  // units that are a target in some stripe
+    for (size_t s = 0; s < stripes; s++) {
+        const uint64_t mask = present[s] & all;
+        const uint64_t wmask = want ? (want[s] & all) : (all & ~mask);
+        if (wmask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+        auto it = ids.find({mask, wmask});
+        if (it == ids.end()) {
+            uint16_t id = 0xFFFF;
+            if (wmask) {
+                uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+                for (size_t i = 0; i < n; i++) pres[i] = (mask >> i) & 1;
+                ReconPlan rp;
+                rp.plan = cached_plan(c, pres);
+                if (rp.plan->rec_status != HEC_OK) return rp.plan->rec_status;
+                rp.rows = target_rows(*rp.plan, true, wmask);
+                if (plans.size() >= 0xFFFF) return HEC_ERR_INVALID_ARG;
+                id = uint16_t(plans.size());
+                max_e = std::max(max_e, rp.rows.size());
+                target_units |= wmask;
+                plans.push_back(std::move(rp));
+            }
+            it = ids.emplace(std::make_pair(mask, wmask), id).first;
+        }
+        stripe_plan[s] = it->second;
+    }
+    if (plans.empty()) return HEC_OK;
+    if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (((target_units >> i) & 1) && !d_out[i]) return HEC_ERR_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+
+    // Any shape, and plans past the kernel's resident LDS: one uniform-pattern
+    // launch per run of consecutive stripes sharing a plan (as the mixed
+    // decode does for the shapes it cannot fuse).
+    auto per_run = [&]() -> int {
+        size_t s0 = 0;
+        while (s0 < stripes) {
+            size_t s1 = s0 + 1;
+            while (s1 < stripes && stripe_plan[s1] == stripe_plan[s0]) s1++;
+            if (stripe_plan[s0] != 0xFFFF) {
+                const ReconPlan& rp = plans[stripe_plan[s0]];
+                Targets t;
+                gather_targets(*rp.plan, k, rp.rows, t);
+                const uint8_t* in[HEC_MAX_DATA_UNITS];
+                size_t ist[HEC_MAX_DATA_UNITS];
+                uint8_t* out[HEC_MAX_PARITY_UNITS];
+                size_t ost[HEC_MAX_PARITY_UNITS];
+                for (size_t r = 0; r < k; r++) {
+                    const size_t u = rp.plan->rec_survivors[r];
+                    in[r] = d_shards[u] + s0 * shard_strides[u];
+                    ist[r] = shard_strides[u];
+                }
+                for (size_t r = 0; r < t.units.size(); r++) {
+                    const size_t u = t.units[r];
+                    out[r] = d_out[u] + s0 * out_strides[u];
+                    ost[r] = out_strides[u];
+                }
+                const int rc = matmul_batch(c->device, t.matrix, t.units.size(), k, in, ist, out, ost, cell_len,
+                                            s1 - s0, stream);
+                if (rc != HEC_OK) return rc;
+            }
+            s0 = s1;
+        }
+        return HEC_OK;
+    };
+
+    bool aligned = cell_len % 16 == 0 && cell_len <= 0xFFFFFFFFull;  // 32-bit lane offsets into a cell
+    for (size_t i = 0; i < n; i++) {
+        aligned &= ((reinterpret_cast<uintptr_t>(d_shards[i]) | shard_strides[i]) & 15u) == 0;
+        if ((target_units >> i) & 1) aligned &= ((reinterpret_cast<uintptr_t>(d_out[i]) | out_strides[i]) & 15u) == 0;
+    }
+    // 2. workspace image: per-stripe plan offsets | plan blobs | zeroed counters
+    const size_t blob_pos = align_up(stripes * sizeof(uint32_t));
+    size_t blob_bytes = 0;
+    std::vector<uint32_t> plan_off(plans.size());
+    for (size_t pi = 0; pi < plans.size(); pi++) {
+        plan_off[pi] = uint32_t(blob_bytes);
+        blob_bytes += sizeof(hec::DevPlanHeader) + plans[pi].rows.size() * k * sizeof(hec::PermTable);
+    }
+    const bool fused = aligned && (k == 2 || k == 3 || k == 6 || k == 10) &&
+                       hec::reconstruct_mixed_resident(stripes, blob_bytes);
+    if (!fused) return per_run();
+
+    const size_t queue_pos = align_up(blob_pos + blob_bytes);
+    const size_t need = queue_pos + hec::kMixedQueueBytes;
+    if (!d_workspace || workspace_bytes < need) return HEC_ERR_INVALID_ARG;
+    {
+        // one of the coder's two pinned images (shared with the mixed decode),
+        // free once its last copy has run
+        std::lock_guard<std::mutex> lk(c->mixed_mu);
+        const int b = c->mixed_next;
+        c->mixed_next ^= 1;
+        if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
+        else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
+        if (c->mixed_host_bytes[b] < need) {
+            if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
+            c->mixed_host[b] = nullptr;
+            c->mixed_host_bytes[b] = 0;
+            const size_t grow = std::max(need, 2 * c->mixed_host_bytes[b ^ 1]);
+            HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), grow, hipHostMallocDefault),
+                    HEC_ERR_NO_MEMORY);
+            c->mixed_host_bytes[b] = grow;
+        }
+        uint8_t* host = c->mixed_host[b];
+        uint32_t* soff = reinterpret_cast<uint32_t*>(host);
+        for (size_t s_ = 0; s_ < stripes; s_++)
+            soff[s_] = stripe_plan[s_] == 0xFFFF ? hec::kNoPlan : plan_off[stripe_plan[s_]];
+        std::memset(host + stripes * sizeof(uint32_t), 0, blob_pos - stripes * sizeof(uint32_t));
+        for (size_t pi = 0; pi < plans.size(); pi++) {
+            const DecodePlan& p = *plans[pi].plan;
+            const std::vector<size_t>& rows = plans[pi].rows;
+            uint8_t* at = host + blob_pos + plan_off[pi];
+            auto* hdr = reinterpret_cast<hec::DevPlanHeader*>(at);
+            std::memset(hdr, 0, sizeof(*hdr));
+            hdr->e = uint32_t(rows.size());
+            for (size_t r = 0; r < k; r++) hdr->surv[r] = uint8_t(p.rec_survivors[r]);
+            for (size_t r = 0; r < rows.size(); r++) {
+                hdr->miss[r] = uint8_t(p.lost[rows[r]]);
+                std::memcpy(at + sizeof(hec::DevPlanHeader) + r * k * sizeof(hec::PermTable),
+                            &p.rec_perm[rows[r] * k * 8], k * sizeof(hec::PermTable));
+            }
+        }
+        std::memset(host + blob_pos + blob_bytes, 0, need - (blob_pos + blob_bytes));  // pad + zeroed counters
+        HEC_HIP(hipMemcpyAsync(d_workspace, host, need, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
+        HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
+    }
+
+    // 3. one launch per group of <= 4 target rows
+    hec::ReconArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t i = 0; i < n; i++) {
+        a.base[i] = d_shards[i];
+        a.stride[i] = shard_strides[i];
+        if ((target_units >> i) & 1) {
+            a.out[i] = d_out[i];
+            a.out_stride[i] = out_strides[i];
+        }
+    }
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
+    a.plans = ws + blob_pos;
+    a.blob_bytes = uint32_t(blob_bytes);
+    a.k = int32_t(k);
+    a.cell_len = cell_len;
+    a.stripes = stripes;
+    for (size_t r0 = 0; r0 < max_e; r0 += hec::kMaxR) {
+        a.row0 = int32_t(r0);
+        a.queue = reinterpret_cast<uint32_t*>(ws + queue_pos +
+                                              (r0 / hec::kMaxR) * hec::kMixedQueues * hec::kMixedQueueStride);
+        const int rows = int(std::min(max_e - r0, size_t(hec::kMaxR)));
+        const int rc = hec::launch_reconstruct_mixed(a, rows, c->device, stream);
+        // refused (the runtime would not grant the LDS): every row per run;
+        // rows an earlier launch wrote are written again with the same bytes
+        if (rc == -1) return per_run();
+        if (rc != 0) return to_status(rc);
+    }
+    return HEC_OK;
+}
+
+}  // namespace
+
+int hec_reconstruct_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                                 uint8_t* const* d_out, const size_t* out_strides, const uint64_t* present,
+                                 const uint64_t* want, size_t cell_len, size_t stripes, void* d_workspace,
+                                 size_t workspace_bytes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_device_mixed");
+    if (!c || !d_shards || !shard_strides || !present || cell_len == 0) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;  // every unit needs storage (present in some stripe)
+    return guarded([&] {
+        return mixed_reconstruct_impl(c, d_shards, shard_strides, d_out, out_strides, present, want, cell_len,
+                                      stripes, d_workspace, workspace_bytes, hip_stream);
     });
 }
 

@@ -49,35 +49,6 @@
 
 namespace hec {
 
-namespace {
-// A wave-uniform 64-bit value held in a VGPR (e.g. from a broadcast LDS
-// read) moved into an SGPR pair (readfirstlane is int -> int: both halves
-// go through uint32_t, no sign extension).
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v))));
-    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v >> 32))));
-    return uint64_t(lo) | (uint64_t(hi) << 32);
-}
-
-// Global-address-space byte pointers for bases that arrive as integers
-// (the mixed kernel's LDS shard table): a generic pointer made from an
-// integer compiles to flat_load / flat_store, which count in lgkmcnt as well
-// as vmcnt, so every LDS wait of the tile (plan, tables) also waited for the
-// cells in flight.  Global pointers keep them global_load / global_store.
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) u32x4 gu32x4;
-
-__device__ __forceinline__ const gbyte* gptr(uint64_t a) { return reinterpret_cast<const gbyte*>(a); }
-__device__ __forceinline__ gbyte* gptr_w(uint64_t a) { return reinterpret_cast<gbyte*>(a); }
-
-__device__ __forceinline__ u32x4 gload16(const gbyte* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const gu32x4*>(p));
-}
-__device__ __forceinline__ void gstore16(gbyte* p, u32x4 v) {
-    __builtin_nontemporal_store(v, reinterpret_cast<gu32x4*>(p));
-}
-}  // namespace
-
 // ---------------------------------------------------------------------------
 // Vector kernel: 16 B per lane per shard, U column chunks per lane (chunk u
 // of a tile is a contiguous BS-lane slab: a wave's U pieces are BS*16 B

@@ -125,6 +125,41 @@ int queue_keyed_by_id();
 // and cell_len % 16 == 0.  0 ok, -1 unsupported, >0 hipError_t.
 int launch_decode_mixed(const MixedArgs& a, int rows, int device, hipStream_t stream);
 
+// ---- reconstruction: any lost unit of a stripe, parity included ------------
+// Argument block of gf_reconstruct_mixed (ec_reconstruct.hip).  The workspace
+// and the plan blobs are laid out as for MixedArgs; a plan's header holds the
+// stripe's e TARGET units in miss[] (unit indices 0 .. k+m-1, ascending) and
+// its rows are the targets' rows over the survivors.  Outputs are addressed
+// by unit index: all k+m of them.
+struct ReconArgs {
+    const uint8_t* base[kMaxShards];  // all k+m unit bases
+    uint64_t stride[kMaxShards];
+    uint8_t* out[kMaxShards];         // rebuilt unit t -> out[t] (may be base[t]: repair in place)
+    uint64_t out_stride[kMaxShards];
+    const uint8_t* plans;             // blob: plan of stripe s at plans + stripe_off[s]
+    const uint32_t* stripe_off;       // per stripe; kNoPlan = no target
+    uint32_t blob_bytes;
+    int32_t k;
+    int32_t row0;                     // first target row handled by this launch
+    uint64_t cell_len;
+    uint64_t stripes;
+    uint32_t chunks, tiles_per_stripe, total_tiles, group, grouped_tiles;
+    uint32_t drain;                   // 1 = wait for a tile's stores before the next tile
+    uint32_t* queue;                  // this launch's zeroed tile counters
+};
+
+// Mixed-pattern reconstruction of one group of target rows row0 ..
+// row0+rows-1 (rows <= kMaxR), plans resident in LDS.  Requires k in
+// {2,3,6,10}, 16-B aligned bases/strides, cell_len % 16 == 0, the launch
+// counters (a.queue) and plan offsets + blob within the resident LDS budget.
+// 0 ok, -1 unsupported (nothing was launched), >0 hipError_t.
+int launch_reconstruct_mixed(const ReconArgs& a, int rows, int device, hipStream_t stream);
+// That budget: plan offsets (u32 per stripe, 16-B padded) + plan blob.  gfx950
+// has 160 KiB of LDS per CU and the kernel's static LDS is 1.5 KiB.
+constexpr uint64_t kReconResidentMax = 156u << 10;
+// True when a batch's plan offsets and blob fit it.
+bool reconstruct_mixed_resident(uint64_t stripes, uint64_t blob_bytes);
+
 // True when the launch's coefficients are the RS coding matrix's parity rows
 // (gen_rs_matrix, gf256.rs:40-57) for its (k, r): the encode kernels then
 // run the bit-sliced XOR networks of xor_networks.hpp.

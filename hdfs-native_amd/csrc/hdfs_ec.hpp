@@ -118,6 +118,49 @@ class Coder {
             if (!data[i]) data[i] = std::move(rec[i]);
     }
 
+    // Hadoop RSRawDecoder.decode(inputs, erasedIndexes, outputs) -- no
+    // counterpart in the reference, whose decode leaves parity None: fills
+    // every missing slot, data or parity, in place.  `want` narrows it to
+    // some of the missing unit indices (the others stay None); naming a
+    // present unit throws std::invalid_argument.
+    void reconstruct(std::vector<std::optional<Bytes>>& data, const std::vector<size_t>* want = nullptr) const {
+        const size_t units = k_ + m_;
+        if (data.size() != units) throw std::invalid_argument("reconstruct: need data_units + parity_units slots");
+        std::vector<uint8_t> want_flags(units, 0);
+        if (want)
+            for (size_t t : *want) {
+                if (t >= units) throw std::invalid_argument("reconstruct: want index out of range");
+                if (data[t]) throw std::invalid_argument("reconstruct: want names a present unit");
+                want_flags[t] = 1;
+            }
+        size_t n = 0;
+        bool any = false, any_target = false;
+        for (size_t i = 0; i < units; i++) {
+            if (data[i]) {
+                n = data[i]->size();
+                any = true;
+            } else if (!want || want_flags[i]) {
+                any_target = true;
+            }
+        }
+        if (!any_target) return;
+        if (!any) check(HEC_ERR_NOT_ENOUGH_SHARDS);
+        std::vector<const uint8_t*> in(units, nullptr);
+        std::vector<Bytes> rec(units);
+        std::vector<uint8_t*> out(units, nullptr);
+        for (size_t i = 0; i < units; i++) {
+            if (data[i]) {
+                in[i] = data[i]->data();
+            } else if (!want || want_flags[i]) {
+                rec[i].resize(n);
+                out[i] = rec[i].data();
+            }
+        }
+        check(hec_reconstruct(h_.get(), in.data(), n, want ? want_flags.data() : nullptr, out.data()));
+        for (size_t i = 0; i < units; i++)
+            if (out[i]) data[i] = std::move(rec[i]);
+    }
+
    private:
     struct Deleter {
         void operator()(hec_coder_t* c) const { hec_coder_destroy(c); }

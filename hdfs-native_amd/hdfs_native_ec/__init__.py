@@ -56,6 +56,8 @@ EXPORTS = [
     "hec_coder_host_limit", "hec_gf_matmul_host", "hec_host_isa", "hec_encode_rows_host",
     "hec_coder_prepare_decode", "hec_jit_warm", "hec_jit_stats", "hec_queue_stats",
     "hec_encode_rows_workspace_size", "hec_encode_rows_device", "hec_decode_rows_host",
+    "hec_reconstruct_plan", "hec_reconstruct", "hec_reconstruct_device",
+    "hec_reconstruct_mixed_workspace_size", "hec_reconstruct_device_mixed",
 ]
 
 
@@ -168,6 +170,12 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_encode_rows_workspace_size": ([P, S], S),
         "hec_encode_rows_device": ([P, P, S, P, S, P, S, P], I),
         "hec_decode_rows_host": ([P, PP, SP, S, P, S, S], I),
+        "hec_reconstruct_plan": ([ctypes.c_char_p, S, S, P, P, SP, SP, SP, P], I),
+        "hec_reconstruct": ([P, PP, S, P, PP], I),
+        "hec_reconstruct_device": ([P, PP, SP, PP, SP, P, S, S, P], I),
+        "hec_reconstruct_mixed_workspace_size": ([P, S], S),
+        "hec_reconstruct_device_mixed": ([P, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64), S, S, P, S, P], I),
     }
     if hasattr(lib, "hec_tune_set"):  # the measurement build only (include/hdfs_ec_amd_exp.h)
         sig["hec_tune_set"] = ([I, I], I)
@@ -288,6 +296,30 @@ def decode_plan(data_units: int, parity_units: int, present: Sequence[bool]):
     _check(lib.hec_decode_plan(k, m, pres, ctypes.byref(e), surv, miss, mat))
     e = e.value
     return list(surv) if e else [], list(miss[:e]), [list(mat[r * k:(r + 1) * k]) for r in range(e)]
+
+
+def _want_bytes(n: int, want):
+    """want: None (every missing unit) or the unit indices to rebuild."""
+    if want is None:
+        return None
+    w = set(want)
+    return (ctypes.c_uint8 * n)(*[1 if i in w else 0 for i in range(n)])
+
+
+def reconstruct_plan(data_units: int, parity_units: int, present: Sequence[bool], want=None, codec: str = "rs"):
+    """hec_reconstruct_plan: (survivors, targets, matrix) for rebuilding the
+    missing units of `present` (data or parity); `want` = unit indices to
+    rebuild (None = every missing unit)."""
+    k, m = data_units, parity_units
+    pres = (ctypes.c_uint8 * (k + m))(*[1 if p else 0 for p in present])
+    t = ctypes.c_size_t(0)
+    surv = (ctypes.c_size_t * k)()
+    targ = (ctypes.c_size_t * (k + m))()
+    mat = (ctypes.c_uint8 * ((k + m) * k))()
+    _check(lib.hec_reconstruct_plan(codec.encode(), k, m, pres, _want_bytes(k + m, want), ctypes.byref(t), surv,
+                                    targ, mat))
+    t = t.value
+    return list(surv) if t else [], list(targ[:t]), [list(mat[r * k:(r + 1) * k]) for r in range(t)]
 
 
 ALLOC_DEFAULT = 0
@@ -447,6 +479,29 @@ class Coder:
             if data[i] is None:
                 data[i] = outs[i].tobytes()
 
+    def reconstruct(self, data: List[Optional[bytes]], want=None) -> None:
+        """hec_reconstruct: fills the missing slots of `data`, data or parity,
+        in place (Hadoop RSRawDecoder.decode); `want` = the unit indices to
+        rebuild (None = every missing one; the others stay None)."""
+        import numpy as np
+        n_units = self.data_units + self.parity_units
+        assert len(data) == n_units
+        present = [d for d in data if d is not None]
+        targets = [i for i in range(n_units) if data[i] is None and (want is None or i in set(want))]
+        if want is not None and any(data[i] is not None for i in want):
+            _check(HEC_ERR_INVALID_ARG)
+        if not present:
+            _check(HEC_ERR_NOT_ENOUGH_SHARDS if targets else HEC_OK)
+            return
+        n = len(present[0])
+        ins = [None if d is None else np.ascontiguousarray(np.frombuffer(bytes(d), dtype=np.uint8)) for d in data]
+        outs = [np.empty(n, dtype=np.uint8) if i in targets else None for i in range(n_units)]
+        _check(self._lib.hec_reconstruct(self._h, _pp([0 if a is None else a.ctypes.data for a in ins]), n,
+                                         _want_bytes(n_units, want),
+                                         _pp([0 if a is None else a.ctypes.data for a in outs])))
+        for i in targets:
+            data[i] = outs[i].tobytes()
+
     def prepare_decode(self, missing: Sequence[int], checksum_type: int = 2) -> bool:
         """hec_coder_prepare_decode: compile the plan-specialised fused decode
         + verify kernel for shards `missing` unavailable, now; True when it
@@ -510,6 +565,29 @@ class Coder:
                                            _sp(out_strides), masks, cell_len, stripes,
                                            ctypes.c_void_p(workspace_ptr), workspace_bytes,
                                            ctypes.c_void_p(stream)))
+
+    def reconstruct_device(self, shard_ptrs, shard_strides, out_ptrs, out_strides, cell_len, stripes, want=None,
+                           stream: int = 0) -> None:
+        """hec_reconstruct_device: shard_ptrs[k+m] (None = missing), out_ptrs
+        [k+m] (used at the targets; may be the lost unit's own slot)."""
+        _check(self._lib.hec_reconstruct_device(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides),
+                                                _pp([p or 0 for p in out_ptrs]), _sp(out_strides),
+                                                _want_bytes(len(shard_ptrs), want), cell_len, stripes,
+                                                ctypes.c_void_p(stream)))
+
+    def reconstruct_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_reconstruct_mixed_workspace_size(self._h, stripes)
+
+    def reconstruct_device_mixed(self, shard_ptrs, shard_strides, out_ptrs, out_strides, present_masks, want_masks,
+                                 cell_len, stripes, workspace_ptr, workspace_bytes, stream: int = 0) -> None:
+        """hec_reconstruct_device_mixed: per-stripe presence masks and (or
+        None: everything missing) per-stripe masks of the units to rebuild."""
+        masks = (ctypes.c_uint64 * stripes)(*present_masks)
+        wants = None if want_masks is None else (ctypes.c_uint64 * stripes)(*want_masks)
+        _check(self._lib.hec_reconstruct_device_mixed(self._h, _pp(shard_ptrs), _sp(shard_strides),
+                                                      _pp([p or 0 for p in out_ptrs]), _sp(out_strides), masks,
+                                                      wants, cell_len, stripes, ctypes.c_void_p(workspace_ptr),
+                                                      workspace_bytes, ctypes.c_void_p(stream)))
 
     def gf_matmul_device(self, matrix: List[List[int]], in_ptrs, in_strides, out_ptrs, out_strides, cell_len,
                          stripes, stream: int = 0) -> None:
@@ -673,6 +751,27 @@ def decode_batch_mixed(coder: Coder, data, parity, present_masks: Sequence[int],
         workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=data.device)
     coder.decode_device_mixed(dp + pp, ds + ps, op, os_, list(present_masks), data.shape[2], S,
                               workspace.data_ptr(), workspace.numel(), s.cuda_stream)
+    return workspace
+
+
+def reconstruct_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], want_masks=None, stream=None,
+                            workspace=None):
+    """Repair in place: cells is a uint8 cuda tensor [S, k+m, cell] holding
+    every unit of every stripe; present_masks[s] bit i = unit i of stripe s is
+    intact.  The lost units (or those in want_masks[s]) are rebuilt into their
+    own slots, data and parity alike.  Returns the workspace (reusable once
+    the stream has passed the call)."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    nbytes = coder.reconstruct_mixed_workspace_size(S)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=cells.device)
+    coder.reconstruct_device_mixed(ptrs, strides, ptrs, strides, list(present_masks),
+                                   None if want_masks is None else list(want_masks), cells.shape[2], S,
+                                   workspace.data_ptr(), workspace.numel(), s.cuda_stream)
     return workspace
 
 

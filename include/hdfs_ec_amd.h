@@ -222,6 +222,83 @@ int hec_decode_device_mixed(hec_coder_t *coder, const uint8_t *const *d_shards, 
                             size_t cell_len, size_t stripes, void *d_workspace, size_t workspace_bytes,
                             void *hip_stream);
 
+/* ---- Reconstruction: any lost unit of a stripe, parity included --------- *
+ * What block-group repair needs (Hadoop RSRawDecoder.decode(inputs,
+ * erasedIndexes, outputs)): when a DataNode dies, each block group it held
+ * loses a different unit index, about m/(k+m) of them parity units.  The
+ * reference's reader never rebuilds parity (gf256.rs:96-97), so these calls
+ * have no counterpart there; the decode calls above are unchanged.
+ * Survivors are the first k present units in index order, as hec_decode.  A
+ * lost data unit t is rebuilt with row t of inverse(select_rows(C, survivors)),
+ * a lost parity unit k+j with row  C[k+j] . inverse(select_rows(C, survivors)).
+ * `want` (where taken) narrows the work to some of the lost units. */
+
+/* The plan for a presence mask (host only, no device).  codec as
+ * hec_coder_create_codec (NULL = "rs"); k+m <= 64.  present[k+m]: non-zero =
+ * unit available.  want[k+m]: non-zero = rebuild this unit; NULL = every
+ * missing unit; a want entry set on a present unit -> HEC_ERR_INVALID_ARG.
+ * On HEC_OK:
+ *   *n_targets   = t, the number of units to rebuild (0 => nothing to do, also
+ *                  when fewer than k units are present);
+ *   survivors[k] = the first k present unit indices, ascending;
+ *   targets[t]   = the units to rebuild, ascending (t <= m);
+ *   matrix[t*k]  = their rows over the survivors, row-major; for data units
+ *                  byte-identical to hec_decode_plan's.
+ * HEC_ERR_NOT_ENOUGH_SHARDS when t > 0 and fewer than k units are present
+ * (*n_targets is still set; nothing else is written). */
+int hec_reconstruct_plan(const char *codec, size_t data_units, size_t parity_units,
+                         const uint8_t *present, const uint8_t *want,
+                         size_t *n_targets, size_t *survivors, size_t *targets, uint8_t *matrix);
+
+/* Host drop-in (synchronous).  shards[k+m] host buffers of shard_len bytes,
+ * NULL = missing; want[k+m] as above (NULL = every missing unit).  out[k+m]:
+ * for every target t, out[t] points to shard_len writable bytes and receives
+ * the rebuilt unit (NULL there -> HEC_ERR_INVALID_ARG); the other entries are
+ * never read or written.  Routed like hec_decode (hec_coder_set_host_limit;
+ * a host-only coder always runs the host routine).  Any shard_len >= 1.
+ * HEC_OK without writing when there is no target, HEC_ERR_NOT_ENOUGH_SHARDS
+ * (nothing written) with a target and fewer than k units present. */
+int hec_reconstruct(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len,
+                    const uint8_t *want, uint8_t *const *out);
+
+/* Device-resident batch with one pattern for the whole batch (asynchronous
+ * on hip_stream).  d_shards[k+m] (NULL = missing) with shard_strides[k+m];
+ * d_out[k+m] with out_strides[k+m], used only at target indices.  d_out[t]
+ * may be the lost unit's own storage slot (repair in place); a NULL d_out at
+ * a target -> HEC_ERR_INVALID_ARG, nothing launched.  Four rows per launch.  With every data unit present and all m parity units the targets,
+ * the rows are the coding matrix's parity rows and the call runs the encode
+ * kernels: the same bytes as hec_encode_device. */
+int hec_reconstruct_device(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
+                           uint8_t *const *d_out, const size_t *out_strides, const uint8_t *want,
+                           size_t cell_len, size_t stripes, void *hip_stream);
+
+/* Device-resident batch where every stripe has its OWN pattern: the shape of
+ * a repair batch after a node failure.  d_shards[k+m] / shard_strides[k+m]:
+ * storage of every unit index (never NULL; slots a stripe lacks are not
+ * read).  present[stripes] (host): bit i set = unit i of that stripe is
+ * available.  want[stripes] (host): bit t set = rebuild unit t of that stripe;
+ * NULL = everything the stripe lacks; a bit on a present unit ->
+ * HEC_ERR_INVALID_ARG.  Rebuilt unit t of stripe s goes to d_out[t] +
+ * s*out_strides[t]; d_out[t] is needed only for units that are a target in
+ * some stripe and may alias d_shards[t].  One plan per distinct (present,
+ * want) pair is uploaded to d_workspace (hec_reconstruct_mixed_workspace_size
+ * bytes; keep it untouched until the stream reaches the work: the launch
+ * keeps its tile counters there, so calls in flight at once need different
+ * workspaces).  One kernel per 4 target rows for k in {2,3,6,10} with 16-B
+ * aligned bases, strides and cell_len and plans that fit the kernel's LDS;
+ * other shapes run one hec_reconstruct_device-style launch per run of
+ * consecutive stripes sharing a plan (same results) and never touch the
+ * workspace, which may then be NULL; its size is bounded by what the kernel's
+ * LDS can hold, whatever the stripe count.  If any stripe has a
+ * target and fewer than k units present, HEC_ERR_NOT_ENOUGH_SHARDS is
+ * returned and nothing is launched. */
+size_t hec_reconstruct_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+int hec_reconstruct_device_mixed(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
+                                 uint8_t *const *d_out, const size_t *out_strides,
+                                 const uint64_t *present, const uint64_t *want,
+                                 size_t cell_len, size_t stripes, void *d_workspace, size_t workspace_bytes,
+                                 void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

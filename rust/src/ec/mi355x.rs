@@ -86,6 +86,19 @@ unsafe extern "C" {
     fn hec_decode_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
                          d_out: *const *mut u8, out_strides: *const usize, cell_len: usize, stripes: usize,
                          stream: *mut c_void) -> c_int;
+    fn hec_reconstruct(c: *mut HecCoder, shards: *const *const u8, n: usize, want: *const u8,
+                       out: *const *mut u8) -> c_int;
+    fn hec_reconstruct_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
+                              d_out: *const *mut u8, out_strides: *const usize, want: *const u8, cell_len: usize,
+                              stripes: usize, stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_plan(codec: *const c_char, k: usize, m: usize, present: *const u8, want: *const u8,
+                            n_targets: *mut usize, survivors: *mut usize, targets: *mut usize,
+                            matrix: *mut u8) -> c_int;
+    fn hec_reconstruct_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_reconstruct_device_mixed(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
+                                    d_out: *const *mut u8, out_strides: *const usize, present: *const u64,
+                                    want: *const u64, cell_len: usize, stripes: usize, d_workspace: *mut c_void,
+                                    workspace_bytes: usize, stream: *mut c_void) -> c_int;
     fn hec_device_alloc(device: c_int, bytes: usize, flags: u32, out: *mut *mut c_void) -> c_int;
     fn hec_device_free(device: c_int, ptr: *mut c_void) -> c_int;
     fn hec_device_copy(device: c_int, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;
@@ -194,6 +207,65 @@ impl GpuCoder {
         })
     }
 
+    /// Batched reconstruction on stripes already in HBM
+    /// (`hec_reconstruct_device`), one pattern for the batch: `shards[k+m]`
+    /// (null = missing); every missing unit, data or parity, that `want`
+    /// names (`None` = all of them) is rebuilt into `out[t]`, which may be the
+    /// unit's own storage slot (the other `out` slots are never written; null
+    /// is fine there).  What a repair worker calls; the reader never does.
+    /// `Err(ErasureCodingError)` when fewer than k units are present.
+    ///
+    /// # Safety
+    /// As `encode_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_device(&self, shards: &[*const u8], shard_strides: &[usize], out: &[*mut u8],
+                                     out_strides: &[usize], want: Option<&[usize]>, cell: usize, stripes: usize,
+                                     stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        let flags = want.map(|w| want_flags(n, w));
+        check(unsafe {
+            hec_reconstruct_device(self.raw, shards.as_ptr(), shard_strides.as_ptr(), out.as_ptr(),
+                                   out_strides.as_ptr(), flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()),
+                                   cell, stripes, stream)
+        })
+    }
+
+    /// Device bytes `reconstruct_device_mixed` needs for `stripes` stripes.
+    pub fn reconstruct_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_reconstruct_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// A repair batch (`hec_reconstruct_device_mixed`): every stripe has its
+    /// own loss pattern.  `shards[k+m]` is the storage of every unit (never
+    /// null); `present[s]` bit i = unit i of stripe s is intact; `want[s]`
+    /// (`None` = everything the stripe lacks) bit t = rebuild unit t.  Rebuilt
+    /// unit t of stripe s goes to `out[t] + s * out_strides[t]`, which may be
+    /// `shards[t]`'s slot (repair in place); `out[t]` may be null for units no
+    /// stripe rebuilds.  `workspace` is device memory of
+    /// `reconstruct_mixed_workspace_size(stripes)` bytes, untouched until
+    /// `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `encode_device`; `workspace` valid for `workspace_bytes` on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_device_mixed(&self, shards: &[*const u8], shard_strides: &[usize], out: &[*mut u8],
+                                           out_strides: &[usize], present: &[u64], want: Option<&[u64]>,
+                                           cell: usize, workspace: *mut c_void, workspace_bytes: usize,
+                                           stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        assert!(want.map_or(true, |w| w.len() == present.len()), "one want mask per stripe");
+        check(unsafe {
+            hec_reconstruct_device_mixed(self.raw, shards.as_ptr(), shard_strides.as_ptr(), out.as_ptr(),
+                                         out_strides.as_ptr(), present.as_ptr(),
+                                         want.map_or(std::ptr::null(), |w| w.as_ptr()), cell, present.len(),
+                                         workspace, workspace_bytes, stream)
+        })
+    }
+
     /// Waits for `stream` (null = the default stream) on the coder's device.
     pub fn synchronize(&self, stream: *mut c_void) -> Result<()> {
         check(unsafe { hec_device_synchronize(self.device, stream) })
@@ -207,6 +279,13 @@ impl GpuCoder {
     /// `Coder::decode` (gf256.rs:84-137): rebuilds every missing data slot.
     pub fn decode(&self, data: &mut [Option<Bytes>]) -> Result<()> {
         decode_raw(self.raw, self.data_units, self.parity_units, data)
+    }
+
+    /// Hadoop's `RSRawDecoder.decode` (`hec_reconstruct`): rebuilds every
+    /// missing slot, data or parity, that `want` names (`None` = all of
+    /// them); the reference's `decode` above leaves parity `None`.
+    pub fn reconstruct(&self, data: &mut [Option<Bytes>], want: Option<&[usize]>) -> Result<()> {
+        reconstruct_raw(self.raw, self.data_units, self.parity_units, data, want)
     }
 
     /// A whole file in file order (rows of k cells, the last one possibly
@@ -380,6 +459,74 @@ fn decode_raw(raw: *mut HecCoder, k: usize, m: usize, data: &mut [Option<Bytes>]
     let outs: Vec<*mut u8> =
         rec.iter_mut().map(|r| r.as_mut().map_or(std::ptr::null_mut(), |b| b.as_mut_ptr())).collect();
     check(unsafe { hec_decode(raw, ins.as_ptr(), n, outs.as_ptr()) })?;
+    for (i, r) in rec.into_iter().enumerate() {
+        if let Some(b) = r {
+            data[i] = Some(b.freeze());
+        }
+    }
+    Ok(())
+}
+
+fn want_flags(n: usize, want: &[usize]) -> Vec<u8> {
+    let mut flags = vec![0u8; n];
+    for &t in want {
+        assert!(t < n, "want names unit {t} of {n}");
+        flags[t] = 1;
+    }
+    flags
+}
+
+/// `hec_reconstruct_plan` (host only, no device): `(survivors, targets,
+/// matrix)` for rebuilding the missing units of `present` that `want` names
+/// (`None` = all of them); `matrix` holds one row of k coefficients per target.
+pub fn reconstruct_plan(codec: &str, data_units: usize, parity_units: usize, present: &[bool],
+                        want: Option<&[usize]>) -> Result<(Vec<usize>, Vec<usize>, Vec<u8>)> {
+    let (k, n) = (data_units, data_units + parity_units);
+    assert_eq!(present.len(), n, "present.len() == data_units + parity_units");
+    let name = std::ffi::CString::new(codec).map_err(|_| HdfsError::InvalidArgument(codec.to_string()))?;
+    let pres: Vec<u8> = present.iter().map(|&p| p as u8).collect();
+    let flags = want.map(|w| want_flags(n, w));
+    let (mut nt, mut surv, mut targets, mut matrix) = (0usize, vec![0usize; k], vec![0usize; n], vec![0u8; n * k]);
+    check(unsafe {
+        hec_reconstruct_plan(name.as_ptr(), data_units, parity_units, pres.as_ptr(),
+                             flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()), &mut nt, surv.as_mut_ptr(),
+                             targets.as_mut_ptr(), matrix.as_mut_ptr())
+    })?;
+    if nt == 0 {
+        surv.clear();
+    }
+    targets.truncate(nt);
+    matrix.truncate(nt * k);
+    Ok((surv, targets, matrix))
+}
+
+fn reconstruct_raw(raw: *mut HecCoder, k: usize, m: usize, data: &mut [Option<Bytes>],
+                   want: Option<&[usize]>) -> Result<()> {
+    assert_eq!(data.len(), k + m, "data.len() == data_units + parity_units");
+    let flags = want.map(|w| want_flags(k + m, w));
+    let target = |i: usize| data[i].is_none() && flags.as_ref().map_or(true, |f| f[i] != 0);
+    if !(0..k + m).any(target) {
+        // a want on a present unit is the engine's HEC_ERR_INVALID_ARG
+        if let Some(f) = &flags {
+            if (0..k + m).any(|i| f[i] != 0 && data[i].is_some()) {
+                return Err(err(HEC_ERR_INVALID_ARG));
+            }
+        }
+        return Ok(());
+    }
+    let n = match data.iter().flatten().next() {
+        Some(b) => b.len(),
+        None => return Err(err(HEC_ERR_NOT_ENOUGH_SHARDS)),
+    };
+    assert!(n > 0, "shards must not be empty (matrix.rs:57)");
+    assert!(data.iter().flatten().take(k).all(|b| b.len() == n), "equal shard lengths (matrix.rs:215)");
+    let ins: Vec<*const u8> = data.iter().map(|d| d.as_ref().map_or(std::ptr::null(), |b| b.as_ptr())).collect();
+    let mut rec: Vec<Option<BytesMut>> = (0..k + m).map(|i| target(i).then(|| BytesMut::zeroed(n))).collect();
+    let outs: Vec<*mut u8> =
+        rec.iter_mut().map(|r| r.as_mut().map_or(std::ptr::null_mut(), |b| b.as_mut_ptr())).collect();
+    check(unsafe {
+        hec_reconstruct(raw, ins.as_ptr(), n, flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()), outs.as_ptr())
+    })?;
     for (i, r) in rec.into_iter().enumerate() {
         if let Some(b) = r {
             data[i] = Some(b.freeze());
