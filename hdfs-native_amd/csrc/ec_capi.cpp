@@ -1411,6 +1411,67 @@ int hec_reconstruct_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards,
     });
 }
 
+// ---- scrub: verify parity, locate a corrupt unit ---------------------------
+
+int hec_scrub_verdict(uint64_t ruled_out, uint64_t bad_bytes, size_t units, int* unit) {
+    if (units == 0 || units > 64) return HEC_ERR_INVALID_ARG;
+    if (bad_bytes == 0) return HEC_SCRUB_CLEAN;
+    const uint64_t all = units == 64 ? ~uint64_t(0) : (uint64_t(1) << units) - 1;
+    const uint64_t left = ~ruled_out & all;  // the units that explain every bad position
+    if (left == 0) return HEC_SCRUB_MULTIPLE;
+    if ((left & (left - 1)) != 0) return HEC_SCRUB_AMBIGUOUS;
+    if (unit) *unit = __builtin_ctzll(left);
+    return HEC_SCRUB_LOCATED;
+}
+
+int hec_scrub(hec_coder_t* c, const uint8_t* const* shards, size_t shard_len, hec_scrub_result_t* out) {
+    if (!c || !shards || shard_len == 0 || !out) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!shards[i]) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        // always the host routine: the answer is 16 bytes and a pageable row
+        // never pays for PCIe
+        hec::host::scrub(hec::host::best_isa(), c->enc.data() + c->k * c->k, c->enc_aff.data(), c->k, c->m, shards,
+                         shard_len, &out->ruled_out, &out->bad_bytes);
+        return int(HEC_OK);
+    });
+}
+
+int hec_scrub_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
+                     size_t stripes, hec_scrub_result_t* d_results, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_device");
+    if (!c || !d_shards || !shard_strides || cell_len == 0 || !d_results ||
+        (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0)
+        return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > SIZE_MAX / sizeof(hec_scrub_result_t)) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        static_assert(sizeof(hec_scrub_result_t) == 16, "two 64-bit words per stripe");
+        hec::ScrubArgs a;
+        std::memset(&a, 0, sizeof(a));
+        for (size_t i = 0; i < c->k + c->m; i++) {
+            a.base[i] = d_shards[i];
+            a.stride[i] = shard_strides[i];
+        }
+        for (size_t j = 0; j < c->m; j++)
+            for (size_t i = 0; i < c->k; i++) a.coef[j * hec::kMaxK + i] = c->enc[(c->k + j) * c->k + i];
+        a.k = int32_t(c->k);
+        a.m = int32_t(c->m);
+        a.cell_len = cell_len;
+        a.stripes = stripes;
+        a.results = reinterpret_cast<uint64_t*>(d_results);
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        // the kernels only OR and add into the words: zeroed here, in stream
+        // order (a memset node under capture)
+        HEC_HIP(hipMemsetAsync(d_results, 0, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        return to_status(hec::launch_scrub(a, c->device, stream));
+    });
+}
+
 // Pipelined pinned-host batch, 3 device slots and 3 streams:
 //   h2d stream:     [wait kernel(q-3) done: input slot free] H2D(q)  -> ev_in[slot]
 //   compute stream: [wait ev_in[slot], D2H(q-3) done: output slot free] encode(q) -> ev_k[slot]

@@ -160,6 +160,30 @@ constexpr uint64_t kReconResidentMax = 156u << 10;
 // True when a batch's plan offsets and blob fit it.
 bool reconstruct_mixed_resident(uint64_t stripes, uint64_t blob_bytes);
 
+// ---- scrub: verify a stripe's parity and locate a corrupt unit --------------
+// Argument block of gf_scrub / gf_scrub_bytes (ec_scrub.hip).  Read-only over
+// all k+m units; per stripe two 64-bit words in `results` (hec_scrub_result_t:
+// ruled_out, bad_bytes), zeroed on the stream before the launch.
+struct ScrubArgs {
+    const uint8_t* base[kMaxShards];  // all k+m unit bases, none null
+    uint64_t stride[kMaxShards];
+    uint8_t coef[16 * kMaxK];         // parity block P: row j, column i at [j*kMaxK + i]
+    int32_t k, m;
+    uint64_t cell_len;
+    uint64_t stripes;
+    uint64_t* results;                // [stripes][2], 8-B aligned
+    uint32_t chunks, tiles_per_stripe, total_tiles, group, grouped_tiles;
+    uint32_t drain;                   // as MatmulArgs::drain
+    uint32_t* queue;                  // this launch's zeroed tile counters (nullptr: the fixed order)
+    uint32_t* queue_zero;             // the set this launch zeroes for the stream's next launch
+};
+
+// Scrubs a batch.  The fast kernel takes k in {2,3,6,10}, m <= 4, 16-B aligned
+// bases, strides and cell_len and a parity block whose first row has no zero;
+// everything else runs the byte-granular kernel (same results).  `results`
+// must already be zeroed in stream order.  0 ok, -1 invalid sizes, >0 hipError_t.
+int launch_scrub(const ScrubArgs& a, int device, hipStream_t stream);
+
 // True when the launch's coefficients are the RS coding matrix's parity rows
 // (gen_rs_matrix, gf256.rs:40-57) for its (k, r): the encode kernels then
 // run the bit-sliced XOR networks of xor_networks.hpp.

@@ -161,7 +161,52 @@ class Coder {
             if (out[i]) data[i] = std::move(rec[i]);
     }
 
+    // Scrub (`hdfs debug verifyEC`; no counterpart in the reference): are the
+    // k+m units of a stripe consistent, and if not, which one is wrong?
+    // result.verdict() is HEC_SCRUB_CLEAN / LOCATED (unit set) / AMBIGUOUS /
+    // MULTIPLE; what each proves is in include/hdfs_ec_amd.h.
+    struct ScrubResult {
+        uint64_t ruled_out = 0, bad_bytes = 0;
+        size_t units = 0;
+        std::optional<size_t> unit;  // the located unit, for HEC_SCRUB_LOCATED
+        int verdict() const {
+            int u = -1;
+            return hec_scrub_verdict(ruled_out, bad_bytes, units, &u);
+        }
+    };
+    ScrubResult scrub(const std::vector<Bytes>& units) const {
+        if (units.size() != k_ + m_) throw std::invalid_argument("scrub: need data_units + parity_units units");
+        const size_t n = units[0].size();
+        std::vector<const uint8_t*> in(units.size());
+        for (size_t i = 0; i < units.size(); i++) {
+            if (units[i].size() != n) throw std::invalid_argument("scrub: units of unequal length");
+            in[i] = units[i].data();
+        }
+        hec_scrub_result_t r{};
+        check(hec_scrub(h_.get(), in.data(), n, &r));
+        return make_result(r);
+    }
+    // Device-resident batch, asynchronous on hip_stream: d_results[stripes]
+    // (device memory) is zeroed by the call and receives every stripe's pair;
+    // copy it back and pass each entry to scrub_result().
+    void scrub_device(const std::vector<const uint8_t*>& d_units, const std::vector<size_t>& strides, size_t cell_len,
+                      size_t stripes, hec_scrub_result_t* d_results, void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_device: need data_units + parity_units units");
+        check(hec_scrub_device(h_.get(), d_units.data(), strides.data(), cell_len, stripes, d_results, hip_stream));
+    }
+    ScrubResult scrub_result(const hec_scrub_result_t& r) const { return make_result(r); }
+
    private:
+    ScrubResult make_result(const hec_scrub_result_t& r) const {
+        ScrubResult s;
+        s.ruled_out = r.ruled_out;
+        s.bad_bytes = r.bad_bytes;
+        s.units = k_ + m_;
+        int u = -1;
+        if (hec_scrub_verdict(r.ruled_out, r.bad_bytes, s.units, &u) == HEC_SCRUB_LOCATED) s.unit = size_t(u);
+        return s;
+    }
     struct Deleter {
         void operator()(hec_coder_t* c) const { hec_coder_destroy(c); }
     };

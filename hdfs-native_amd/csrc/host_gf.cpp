@@ -347,5 +347,63 @@ void gf_matmul_split(Isa isa, const uint8_t* mat, const uint64_t* aff, size_t ro
     pool->job = nullptr;
 }
 
+size_t scrub_block_bytes() { return size_t(64) << 10; }
+
+void scrub(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, const uint8_t* const* units, size_t n,
+           uint64_t* ruled_out, uint64_t* bad_bytes) {
+    constexpr size_t kMaxUnits = 64;
+    uint64_t ruled = 0, bad = 0;
+    *ruled_out = *bad_bytes = 0;
+    if (n == 0 || k == 0 || m == 0 || k + m > kMaxUnits) return;
+    const uint64_t all = k + m == 64 ? ~uint64_t(0) : (uint64_t(1) << (k + m)) - 1;
+    const size_t block = std::min(n, scrub_block_bytes());
+    std::vector<uint8_t> scratch(m * block);
+    const uint8_t* in[kMaxUnits];
+    uint8_t* syn[kMaxUnits];
+    for (size_t j = 0; j < m; j++) syn[j] = scratch.data() + j * block;
+    for (size_t o = 0; o < n; o += block) {
+        const size_t len = std::min(block, n - o);
+        for (size_t i = 0; i < k; i++) in[i] = units[i] + o;
+        gf_matmul(isa, P, aff, m, k, in, syn, len);
+        // XOR in the stored parity; `any` collects every syndrome byte of the block
+        uint8_t any = 0;
+        for (size_t j = 0; j < m; j++) {
+            const uint8_t* par = units[k + j] + o;
+            uint8_t* s = syn[j];
+            uint8_t a = 0;
+            for (size_t b = 0; b < len; b++) {
+                s[b] ^= par[b];
+                a |= s[b];
+            }
+            any |= a;
+        }
+        if (!any) continue;  // the clean path ends here
+        for (size_t b = 0; b < len; b++) {
+            uint8_t nz = 0;
+            for (size_t j = 0; j < m; j++) nz |= syn[j][b];
+            if (!nz) continue;
+            bad++;
+            if (ruled == all) continue;
+            for (size_t t = 0; t < k + m; t++) {
+                if ((ruled >> t) & 1) continue;
+                bool out = false;
+                for (size_t j = 1; j < m && !out; j++) {
+                    const uint8_t hj = t < k ? P[j * k + t] : uint8_t(j == t - k);
+                    for (size_t i = 0; i < j; i++) {
+                        const uint8_t hi = t < k ? P[i * k + t] : uint8_t(i == t - k);
+                        if (gf_mul(syn[i][b], hj) != gf_mul(syn[j][b], hi)) {
+                            out = true;
+                            break;
+                        }
+                    }
+                }
+                if (out) ruled |= uint64_t(1) << t;
+            }
+        }
+    }
+    *ruled_out = ruled;
+    *bad_bytes = bad;
+}
+
 }  // namespace host
 }  // namespace hec

@@ -64,5 +64,18 @@ inline void gf_matmul_split(const uint8_t* mat, const uint64_t* aff, size_t rows
     gf_matmul_split(best_isa(), mat, aff, rows, cols, in, out, n);
 }
 
+// Stripe scrub on the host (hec_scrub): with P the m x k parity block
+// (row-major) and H = [P | I_m], the syndromes s_j(b) = sum_i P[j][i] *
+// units[i][b] ^ units[k+j][b] of every byte position b < n.  *bad_bytes =
+// positions with a non-zero syndrome vector; *ruled_out bit t (t < k+m) set
+// when some position's vector is not a GF(2^8) multiple of column t of H (some
+// 2x2 minor s_i * H[j][t] ^ s_j * H[i][t] is non-zero).  The syndromes are
+// computed by gf_matmul in blocks of scrub_block_bytes() per unit into a
+// scratch of m such blocks (the only allocation: nothing grows with n); the
+// locate runs over the non-zero positions only.  k + m <= 64, aff as gf_matmul.
+void scrub(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, const uint8_t* const* units, size_t n,
+           uint64_t* ruled_out, uint64_t* bad_bytes);
+size_t scrub_block_bytes();
+
 }  // namespace host
 }  // namespace hec

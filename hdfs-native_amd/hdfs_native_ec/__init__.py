@@ -32,6 +32,12 @@ HEC_ERR_SINGULAR = -6
 HEC_ERR_CHECKSUM = -7
 HEC_DEVICE_HOST = -2  # host-only coder: the engine's host routine, no GPU needed
 
+# hec_scrub_verdict outcomes
+HEC_SCRUB_CLEAN = 0
+HEC_SCRUB_LOCATED = 1
+HEC_SCRUB_AMBIGUOUS = 2
+HEC_SCRUB_MULTIPLE = 3
+
 # ChecksumTypeProto values (rust/src/proto/hadoop.hdfs.rs:1363)
 CHECKSUM_NULL = 0
 CHECKSUM_CRC32 = 1   # crc CRC_32_CKSUM (connection.rs:37)
@@ -58,6 +64,7 @@ EXPORTS = [
     "hec_encode_rows_workspace_size", "hec_encode_rows_device", "hec_decode_rows_host",
     "hec_reconstruct_plan", "hec_reconstruct", "hec_reconstruct_device",
     "hec_reconstruct_mixed_workspace_size", "hec_reconstruct_device_mixed",
+    "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
 ]
 
 
@@ -176,6 +183,9 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_reconstruct_mixed_workspace_size": ([P, S], S),
         "hec_reconstruct_device_mixed": ([P, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64), S, S, P, S, P], I),
+        "hec_scrub_verdict": ([ctypes.c_uint64, ctypes.c_uint64, S, ctypes.POINTER(I)], I),
+        "hec_scrub": ([P, PP, S, P], I),
+        "hec_scrub_device": ([P, PP, SP, S, S, P, P], I),
     }
     if hasattr(lib, "hec_tune_set"):  # the measurement build only (include/hdfs_ec_amd_exp.h)
         sig["hec_tune_set"] = ([I, I], I)
@@ -320,6 +330,18 @@ def reconstruct_plan(data_units: int, parity_units: int, present: Sequence[bool]
                                     targ, mat))
     t = t.value
     return list(surv) if t else [], list(targ[:t]), [list(mat[r * k:(r + 1) * k]) for r in range(t)]
+
+
+def scrub_verdict(ruled_out: int, bad_bytes: int, units: int):
+    """hec_scrub_verdict: (verdict, unit) for one stripe's scrub result over
+    `units` = k+m units; unit is the located unit for HEC_SCRUB_LOCATED, else
+    None.  LOCATED is exact for up to m-1 corrupt units when m >= 3 and assumes
+    at most one when m == 2 (include/hdfs_ec_amd.h)."""
+    unit = ctypes.c_int(-1)
+    rc = lib.hec_scrub_verdict(ruled_out, bad_bytes, units, ctypes.byref(unit))
+    if rc < 0:
+        _check(rc)
+    return rc, (unit.value if rc == HEC_SCRUB_LOCATED else None)
 
 
 ALLOC_DEFAULT = 0
@@ -501,6 +523,26 @@ class Coder:
                                          _pp([0 if a is None else a.ctypes.data for a in outs])))
         for i in targets:
             data[i] = outs[i].tobytes()
+
+    def scrub(self, shards: Sequence[bytes]):
+        """hec_scrub: (ruled_out, bad_bytes) of one stripe whose k+m units are
+        all present (host routine; see scrub_verdict)."""
+        import numpy as np
+        n_units = self.data_units + self.parity_units
+        assert len(shards) == n_units
+        n = len(shards[0])
+        assert all(len(d) == n for d in shards), "equal shard lengths"
+        ins = [np.ascontiguousarray(np.frombuffer(bytes(d) if not isinstance(d, np.ndarray) else d, dtype=np.uint8))
+               for d in shards]
+        res = (ctypes.c_uint64 * 2)()
+        _check(self._lib.hec_scrub(self._h, _pp([a.ctypes.data for a in ins]), n, res))
+        return int(res[0]), int(res[1])
+
+    def scrub_device(self, shard_ptrs, shard_strides, cell_len, stripes, results_ptr, stream: int = 0) -> None:
+        """hec_scrub_device: shard_ptrs[k+m] (none missing); results_ptr = device
+        memory for `stripes` pairs of uint64 (ruled_out, bad_bytes), zeroed by the call."""
+        _check(self._lib.hec_scrub_device(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides), cell_len,
+                                          stripes, ctypes.c_void_p(results_ptr), ctypes.c_void_p(stream)))
 
     def prepare_decode(self, missing: Sequence[int], checksum_type: int = 2) -> bool:
         """hec_coder_prepare_decode: compile the plan-specialised fused decode
@@ -773,6 +815,21 @@ def reconstruct_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], w
                                    None if want_masks is None else list(want_masks), cells.shape[2], S,
                                    workspace.data_ptr(), workspace.numel(), s.cuda_stream)
     return workspace
+
+
+def scrub_batch(coder: Coder, cells, stream=None):
+    """Scrub every stripe of cells, a uint8 cuda tensor [S, k+m, cell] (the
+    layout reconstruct_batch_mixed takes): -> int64 cuda tensor [S, 2] of
+    (ruled_out, bad_bytes) per stripe, (0, 0) where the stripe is consistent.
+    Read-only over cells; asynchronous on the stream."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    coder.scrub_device(ptrs, strides, cells.shape[2], S, out.data_ptr(), s.cuda_stream)
+    return out
 
 
 def decode_batch(coder: Coder, data, parity, missing: Sequence[int], out, stream=None) -> None:

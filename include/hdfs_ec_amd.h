@@ -299,6 +299,80 @@ int hec_reconstruct_device_mixed(hec_coder_t *coder, const uint8_t *const *d_sha
                                  size_t cell_len, size_t stripes, void *d_workspace, size_t workspace_bytes,
                                  void *hip_stream);
 
+/* ---- Scrub: verify a stripe's parity and locate a corrupt unit ----------- *
+ * What a block scanner or a repair worker asks before and after it rebuilds
+ * (`hdfs debug verifyEC`; dfs.datanode.ec.reconstruct.validation, HDFS-15759):
+ * are the k+m units of a stripe still consistent, and if not, which one is
+ * wrong?  The reference's reader trusts the packet checksums
+ * (connection.rs:477-504) and has no counterpart.  All k+m units must be
+ * present: scrubbing a stripe with missing units is out of scope.
+ *
+ * With C the coder's (k+m) x k matrix (hec_gen_codec_matrix), P = C[k:] and
+ * H = [P | I_m] (column t of H is P[:,t] for a data unit t < k and the unit
+ * vector e_j for parity unit k+j), the syndrome of byte position b is
+ *   s_j(b) = sum_i P[j][i] * u_i(b)  ^  u_{k+j}(b),   j < m.
+ * Per stripe a scrub returns
+ *   bad_bytes = the number of positions b < cell_len with some s_j(b) != 0;
+ *   ruled_out = bit t (t < k+m) set iff some position's syndrome vector is not
+ *               a GF(2^8) multiple of column t of H (some 2x2 minor
+ *               s_i(b)*H[j][t] ^ s_j(b)*H[i][t] is non-zero).  Bits >= k+m are
+ *               0; with m == 1 no bit is ever set (one parity cannot locate);
+ *               a clean stripe gives (0, 0).
+ * hec_scrub_verdict (host only) turns the pair into
+ *   HEC_SCRUB_CLEAN     bad_bytes == 0;
+ *   HEC_SCRUB_LOCATED   exactly one unit of 0..units-1 is not ruled out;
+ *                       *unit (if not NULL) receives it -- written in no other case;
+ *   HEC_SCRUB_MULTIPLE  every unit is ruled out: more than one unit is corrupt;
+ *   HEC_SCRUB_AMBIGUOUS anything else (m == 1, or several candidates left);
+ * units == 0 or > 64 -> HEC_ERR_INVALID_ARG.
+ * What a verdict proves: one corrupt unit t leaves every syndrome vector a
+ * multiple of column t, so it is never ruled out, and every other unit is
+ * ruled out at each bad position (any two columns of H are independent for
+ * m >= 2).  Explaining by a single unit a position where several units are
+ * wrong needs an error of weight >= m there (every m columns of H are
+ * independent: the codes are MDS), so with m >= 3 two corrupt units can never
+ * pass for one and LOCATED is exact for up to m-1 corrupt units; with m == 2,
+ * LOCATED assumes at most one corrupt unit.  CLEAN misses only corruption
+ * that is itself a codeword (>= m+1 units wrong at a position, consistently).
+ * The recipe for a repair worker -- scrub, turn each LOCATED unit into a
+ * `present` mask, hec_reconstruct_device_mixed in place, scrub again -- is in
+ * INTEGRATION.md. */
+typedef struct {
+    uint64_t ruled_out;
+    uint64_t bad_bytes;
+} hec_scrub_result_t;
+
+#define HEC_SCRUB_CLEAN 0
+#define HEC_SCRUB_LOCATED 1
+#define HEC_SCRUB_AMBIGUOUS 2
+#define HEC_SCRUB_MULTIPLE 3
+
+int hec_scrub_verdict(uint64_t ruled_out, uint64_t bad_bytes, size_t units, int *unit);
+
+/* Host drop-in (synchronous).  shards[k+m] host buffers of shard_len bytes,
+ * none NULL; any shard_len >= 1.  Always the engine's host routine, whatever
+ * the host limit (the answer is 16 bytes; a pageable row never pays for PCIe)
+ * and on host-only coders: syndromes in blocks of 64 KiB per unit with the
+ * AVX-512+GFNI / AVX2 / scalar multiply, a scalar locate over the non-zero
+ * positions only, no allocation that grows with shard_len.  HEC_ERR_INVALID_ARG
+ * for a NULL shard, shard_len == 0 or NULL out. */
+int hec_scrub(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len, hec_scrub_result_t *out);
+
+/* Device-resident batch (asynchronous on hip_stream), units laid out as for
+ * hec_encode_device: d_shards[k+m] / shard_strides[k+m], none NULL.  Read-only
+ * over the k+m cells of every stripe -- the bytes hec_encode_device moves --
+ * with no scratch.  d_results[stripes] (device memory, 8-byte aligned) is
+ * zeroed by the call itself (one hipMemsetAsync on the stream; a memset node
+ * under stream capture) and then receives each stripe's pair; clean stripes
+ * cost no write.  k in {2,3,6,10} with m <= 4 and 16-B aligned bases, strides
+ * and cell_len run the register kernel (a sibling of the encode kernel); other
+ * shapes a byte-granular kernel with the same results.  stripes == 0 ->
+ * HEC_OK, nothing queued.  HEC_ERR_INVALID_ARG (nothing queued) for a NULL
+ * unit, cell_len == 0, NULL or misaligned d_results; HEC_ERR_DEVICE on a
+ * host-only coder. */
+int hec_scrub_device(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
+                     size_t cell_len, size_t stripes, hec_scrub_result_t *d_results, void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

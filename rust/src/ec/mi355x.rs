@@ -99,6 +99,10 @@ unsafe extern "C" {
                                     d_out: *const *mut u8, out_strides: *const usize, present: *const u64,
                                     want: *const u64, cell_len: usize, stripes: usize, d_workspace: *mut c_void,
                                     workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    fn hec_scrub_verdict(ruled_out: u64, bad_bytes: u64, units: usize, unit: *mut c_int) -> c_int;
+    fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
+    fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
+                        stripes: usize, d_results: *mut ScrubResult, stream: *mut c_void) -> c_int;
     fn hec_device_alloc(device: c_int, bytes: usize, flags: u32, out: *mut *mut c_void) -> c_int;
     fn hec_device_free(device: c_int, ptr: *mut c_void) -> c_int;
     fn hec_device_copy(device: c_int, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;
@@ -110,6 +114,39 @@ unsafe extern "C" {
                                    stripes: usize, chunk_stripes: usize) -> c_int;
     fn hec_group_decode_host_batch(g: *mut HecGroup, h_vertical: *const *const u8, cell_len: usize,
                                    rows: usize, h_file: *mut u8, chunk_rows: usize) -> c_int;
+}
+
+/// One stripe's scrub result (`hec_scrub_result_t`): bit t of `ruled_out` is
+/// set when some byte position's syndromes cannot come from unit t alone;
+/// `bad_bytes` counts the positions whose syndromes are not all zero.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ScrubResult {
+    pub ruled_out: u64,
+    pub bad_bytes: u64,
+}
+
+/// What a scrub result says about a stripe (`HEC_SCRUB_*`).  `Located` is
+/// exact for up to m-1 corrupt units when m >= 3 and assumes at most one when
+/// m == 2; with one parity unit the answer is never `Located`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum ScrubVerdict {
+    Clean,
+    Located(usize),
+    Ambiguous,
+    Multiple,
+}
+
+/// `hec_scrub_verdict` (host only): the verdict for a stripe of `units` = k+m units.
+pub fn scrub_verdict(result: ScrubResult, units: usize) -> Result<ScrubVerdict> {
+    let mut unit: c_int = -1;
+    match unsafe { hec_scrub_verdict(result.ruled_out, result.bad_bytes, units, &mut unit) } {
+        0 => Ok(ScrubVerdict::Clean),
+        1 => Ok(ScrubVerdict::Located(unit as usize)),
+        2 => Ok(ScrubVerdict::Ambiguous),
+        3 => Ok(ScrubVerdict::Multiple),
+        rc => Err(err(rc)),
+    }
 }
 
 /// The ABI revision this shim is written against (include/hdfs_ec_amd.h).
@@ -264,6 +301,40 @@ impl GpuCoder {
                                          want.map_or(std::ptr::null(), |w| w.as_ptr()), cell, present.len(),
                                          workspace, workspace_bytes, stream)
         })
+    }
+
+    /// Scrubs a device-resident batch (`hec_scrub_device`): are the k+m units
+    /// of every stripe consistent, and if not, which unit is wrong?  All
+    /// `shards[k+m]` present (never null), laid out as for `encode_device`;
+    /// read-only, no scratch.  `results` is device memory for `stripes`
+    /// `ScrubResult`s (8-byte aligned); the call zeroes it on `stream` and the
+    /// kernel fills it.  Copy it back once `stream` has passed the call and
+    /// hand each entry to `scrub_verdict`; a `Located(t)` stripe is repaired by
+    /// `reconstruct_device_mixed` with `present = all & !(1 << t)`, and a second
+    /// scrub confirms it.
+    ///
+    /// # Safety
+    /// As `encode_device`; `results` valid for `stripes * 16` bytes on this device.
+    pub unsafe fn scrub_device(&self, shards: &[*const u8], shard_strides: &[usize], cell: usize, stripes: usize,
+                               results: *mut ScrubResult, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_device(self.raw, shards.as_ptr(), shard_strides.as_ptr(), cell, stripes, results, stream)
+        })
+    }
+
+    /// `hec_scrub` on host buffers: one stripe whose k+m units are all
+    /// present, any length >= 1; always the engine's host routine.
+    pub fn scrub(&self, units: &[Bytes]) -> Result<ScrubResult> {
+        let n = self.data_units + self.parity_units;
+        assert!(units.len() == n, "one buffer per unit");
+        let len = units[0].len();
+        assert!(units.iter().all(|u| u.len() == len), "equal unit lengths");
+        let ptrs: Vec<*const u8> = units.iter().map(|u| u.as_ptr()).collect();
+        let mut out = ScrubResult::default();
+        check(unsafe { hec_scrub(self.raw, ptrs.as_ptr(), len, &mut out) })?;
+        Ok(out)
     }
 
     /// Waits for `stream` (null = the default stream) on the coder's device.
