@@ -1466,8 +1466,8 @@ int hec_scrub_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
         hipStream_t stream = static_cast<hipStream_t>(hip_stream);
         // the kernels only OR and add into the words: zeroed here, in stream
-        // order (a memset node under capture)
-        HEC_HIP(hipMemsetAsync(d_results, 0, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        // order (a zeroing kernel node under capture)
+        HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
         return to_status(hec::launch_scrub(a, c->device, stream));
     });
 }

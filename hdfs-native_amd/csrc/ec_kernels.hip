@@ -1278,8 +1278,8 @@ Shape default_shape(int k, uint64_t cell_len) {
 //    (only the owning thread launches on them).
 //  * Stream capture: a launch into a capturing stream takes a set of its own
 //    from the device's graph pool (allocated outside any capture by
-//    queue_reserve) and a memset node zeroing it is captured right before the
-//    kernel, so every replay starts from zero and no replay shares counters
+//    queue_reserve) and a kernel node zeroing it (zero_async) is captured right
+//    before the kernel, so every replay starts from zero and no replay shares counters
 //    with direct launches on the capture stream or another graph.  Graph sets
 //    are never returned (the graph may be replayed at any time).
 //  * Bounds: kMaxStreamSets streams and kGraphSets graph launches per device.
@@ -1402,6 +1402,33 @@ std::unique_ptr<StreamSets> make_sets() {
 
 int queue_keyed_by_id() { return stream_get_id() ? 1 : 0; }
 
+// 8-byte words, grid-stride: the zeroing a captured launch needs (zero_async)
+__global__ __launch_bounds__(256) void zero_words(unsigned long long* p, uint64_t n) {
+    for (uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x; i < n; i += uint64_t(gridDim.x) * 256u) p[i] = 0ull;
+}
+
+// Not a memset node: the HIP runtime a PyTorch 2.10 / ROCm 7.0 wheel brings
+// replays a captured hipMemsetAsync with whatever its fill pattern's staging
+// memory holds by then -- zeros on the first replay, and a 16-byte pattern of
+// addresses once other launches have gone by (the same with two bare
+// hipMemsetAsync calls in a graph and nothing of this library;
+// tests/test_gpu_scrub_variants.py::test_graph_capture_replay).  A kernel
+// node's arguments are copied into the graph, so a replay zeroes for certain.
+hipError_t zero_async(void* p, size_t bytes, hipStream_t stream) {
+    if (bytes == 0) return hipSuccess;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) (void)hipGetLastError();  // as queue_lease: not capturing
+    if (cap != hipStreamCaptureStatusActive || (reinterpret_cast<uintptr_t>(p) | bytes) % 8 != 0)
+        return hipMemsetAsync(p, 0, bytes, stream);
+    unsigned long long* words = static_cast<unsigned long long*>(p);
+    uint64_t n = bytes / 8;
+    uint64_t grid = (n + 255) / 256;
+    if (grid > 1024) grid = 1024;
+    void* args[] = {&words, &n};
+    return hipLaunchKernel(reinterpret_cast<const void*>(&zero_words), dim3(uint32_t(grid)), dim3(256), args, 0,
+                           stream);
+}
+
 QueueLease queue_lease(int device, hipStream_t stream) {
     QueueLease l;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1418,7 +1445,7 @@ QueueLease queue_lease(int device, hipStream_t stream) {
             if (d.graph_pool && d.graph_next < kGraphSets) set = d.graph_pool + d.graph_next++ * (kSetBytes / 4);
         }
         if (!set) return l;
-        if (hipMemsetAsync(set, 0, kSetBytes, stream) != hipSuccess) {  // captured: a memset node
+        if (zero_async(set, kSetBytes, stream) != hipSuccess) {  // captured: a zeroing kernel node
             (void)hipGetLastError();
             return l;
         }

@@ -91,9 +91,9 @@ struct MixedArgs {
 // stream is held (its sets' lock) from queue_lease() until the lease ends, so
 // launches from several threads on one stream still alternate in their
 // stream order.  A launch into a stream that is being captured gets a set of
-// its own (the graph keeps it for good) zeroed by a memset node captured
-// just before the kernel; `zero` is then nullptr.  An empty lease (use ==
-// nullptr) means: launch the fixed-order kernel.
+// its own (the graph keeps it for good) zeroed by a kernel node (zero_async)
+// captured just before the kernel; `zero` is then nullptr.  An empty lease
+// (use == nullptr) means: launch the fixed-order kernel.
 struct QueueLease {
     uint32_t* use = nullptr;
     uint32_t* zero = nullptr;
@@ -114,6 +114,9 @@ QueueLease queue_lease(int device, hipStream_t stream);
 // (hec_coder_create calls it); a capture with no set left launches the
 // fixed-order kernels.
 void queue_reserve(int device);
+// Zeroes `bytes` at p in stream order: hipMemsetAsync, and under stream
+// capture (8-byte aligned p and bytes) a zeroing kernel node in its place.
+hipError_t zero_async(void* p, size_t bytes, hipStream_t stream);
 // Counter sets in use on a device: {direct streams, graph sets handed out}.
 void queue_stats(int device, uint64_t* streams, uint64_t* graph_sets);
 // 1 when streams are told apart by hipStreamGetId, 0 when by handle.

@@ -20,8 +20,8 @@ namespace {  // per translation unit, as gf_device.hpp
 // never depends on how the previous one counted: the counters are zero at
 // every launch's start by construction, whatever state an earlier launch
 // left them in.  Block 0's first kMixedQueues lanes, vector stores.  Graph
-// launches get a private set zeroed by a memset node instead (zero ==
-// nullptr).
+// launches get a private set zeroed by a kernel node of the graph instead
+// (zero == nullptr).
 __device__ __forceinline__ void queue_zero_next(uint32_t* zero) {
     if (zero && blockIdx.x == 0 && threadIdx.x < kMixedQueues) zero[threadIdx.x * (kMixedQueueStride / 4)] = 0u;
 }
@@ -33,7 +33,7 @@ __device__ __forceinline__ void queue_zero_next(uint32_t* zero) {
 // the wave's next round when it takes one, so the fetch is in flight while
 // the tile is coded.  peek() reads that next tile early (a kernel that
 // prefetches the next tile's inputs) without fetching again.  The counters
-// start at zero (queue_zero_next / the graph's memset node); nothing here
+// start at zero (queue_zero_next / the graph's zeroing node); nothing here
 // resets them, so no count of fetches has to come out exact.
 struct WaveQueue {
     uint32_t* ctr;

@@ -362,8 +362,8 @@ int hec_scrub(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len
  * hec_encode_device: d_shards[k+m] / shard_strides[k+m], none NULL.  Read-only
  * over the k+m cells of every stripe -- the bytes hec_encode_device moves --
  * with no scratch.  d_results[stripes] (device memory, 8-byte aligned) is
- * zeroed by the call itself (one hipMemsetAsync on the stream; a memset node
- * under stream capture) and then receives each stripe's pair; clean stripes
+ * zeroed by the call itself (one hipMemsetAsync on the stream; a zeroing kernel
+ * node under stream capture) and then receives each stripe's pair; clean stripes
  * cost no write.  k in {2,3,6,10} with m <= 4 and 16-B aligned bases, strides
  * and cell_len run the register kernel (a sibling of the encode kernel); other
  * shapes a byte-granular kernel with the same results.  stripes == 0 ->
@@ -470,7 +470,7 @@ void hec_jit_stats(uint64_t *compiled, uint64_t *from_disk, uint64_t *failed, ui
  * The coding kernels deal their tiles from launch counters.  Every stream
  * that launched one has two counter sets it alternates between (each launch
  * zeroes the set of the stream's next launch); a launch into a capturing
- * stream gets a set of its own, zeroed by a memset node in the graph.
+ * stream gets a set of its own, zeroed by a kernel node in the graph.
  * hec_queue_stats: streams with sets and graph sets handed out on `device`
  * (process totals; past 4096 streams / 256 graph launches per device the
  * kernels fall back to their fixed tile order), and *keyed_by_id = 1 when

@@ -671,7 +671,7 @@ def test_work_queue_one_stream_two_threads(dev):
 def test_work_queue_graph_capture_replay(dev, c_oracle):
     """torch.cuda.graph (global capture mode) around an encode and a decode:
     the captured launches take graph counter sets of their own, zeroed by a
-    memset node at every replay.  Replays on the capture stream between
+    kernel node of the graph at every replay.  Replays on the capture stream between
     direct launches there, and on a second stream while the first runs
     direct launches, are all exact against the oracle."""
     k, m, S, cell = 6, 3, 6, 65536 + 48

@@ -6,7 +6,44 @@ when some position's syndrome vector has a non-zero 2x2 minor against column t
 of H = [P | I]); the WHOLE result array is compared, exactly, so a count that
 lands on the wrong stripe or a lane past the cell that is counted shows as
 well as a wrong mask.  Every result buffer is handed in filled with 0xFF: the
-call zeroes it itself."""
+call zeroes it itself.
+
+Which kernel each group of tests reaches (scrub_pick in csrc/ec_scrub.hip
+builds gf_scrub<K, M, U, BS, WQ> for K in {2, 3, 6, 10} x M in {1, 2, 3, 4},
+each with the work queue, WQ > 0, and in the fixed tile order, WQ == 0; a
+kernel added there gets its row here):
+
+  group (test)                                  kernels
+  --------------------------------------------  ---------------------------------
+  REGISTER (test_clean_batch_writes_zeros,      gf_scrub<K, M, .., WQ > 0>, all 16
+    test_corruptions_equal_reference)             (K, M) with rs; M == 1 again with
+                                                  xor at K = 2, 3, 6, 10; rs-legacy
+                                                  at (3,2), (6,3), (10,4); cells
+                                                  around the wave-tile for (6,3)
+                                                  and (10,4)
+  BYTE (the same two tests, test_generic_*)     gf_scrub_bytes: k outside the fast
+                                                  set ((5,3), xor (5,1)), an odd
+                                                  cell length, bases off by a byte
+  test_gpu_scrub_variants.py:
+    test_byte_kernel_shapes                     gf_scrub_bytes at (4,8), (32,16),
+                                                  (6,5) (there because of m alone),
+                                                  (1,2), xor (5,1)
+    test_more_tiles_than_waves                  gf_scrub<3,2 / 6,3 / 10,4, WQ > 0>,
+                                                  every wave through the tile loop
+                                                  at least twice
+    test_stripe_stride_past_4gib                gf_scrub<6,3, WQ > 0> and
+                                                  gf_scrub_bytes, stripe offsets
+                                                  of 2^32 and more
+    test_three_streams_at_once                  gf_scrub<6,3, WQ > 0>, the stream
+                                                  counter sets of three streams
+    test_graph_capture_replay                   gf_scrub<6,3> and <10,4>, WQ > 0 on
+                                                  graph counter sets
+    test_fixed_tile_order_in_child_process      gf_scrub<2,1 / 3,2 / 6,3 / 10,4 /
+      (scrub_fixed_order_child.py)                6,1, WQ == 0> and the fixed-order
+                                                  gf_matmul kernels behind encode,
+                                                  decode and reconstruct, once the
+                                                  graph pool is used up
+"""
 import ctypes
 
 import numpy as np
@@ -20,11 +57,22 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 S = 37  # leaves a remainder stripe after the 4-stripe tile groups
-# (codec, k, m, cell_len, wave-tile bytes): around the wave-tiles of the two shapes
-FAST = [("rs", 6, 3, 16, 4096), ("rs", 6, 3, 4096, 4096), ("rs", 6, 3, 4112, 4096), ("rs", 6, 3, 12336, 4096),
-        ("rs", 10, 4, 16, 2048), ("rs", 10, 4, 2048, 2048), ("rs", 10, 4, 2064, 2048), ("rs", 10, 4, 6160, 2048),
-        ("rs", 3, 2, 4112, 4096), ("xor", 5, 1, 4112, 4096), ("rs-legacy", 6, 3, 4112, 4096)]
+TILE = {2: 4096, 3: 4096, 6: 4096, 10: 2048}  # bytes of a wave-tile of the register kernel, by k
+# (codec, k, m, cell_len, wave-tile bytes).  The register kernel: cells around
+# the wave-tiles of (6,3) and (10,4), then one wave-tile + 16 bytes at all 16
+# (k, m) it is built for, the M == 1 kernels again with xor, and rs-legacy
+REGISTER = [("rs", 6, 3, 16, 4096), ("rs", 6, 3, 4096, 4096), ("rs", 6, 3, 12336, 4096),
+            ("rs", 10, 4, 16, 2048), ("rs", 10, 4, 2048, 2048), ("rs", 10, 4, 6160, 2048)]
+REGISTER += [("rs", k, m, TILE[k] + 16, TILE[k]) for k in (2, 3, 6, 10) for m in (1, 2, 3, 4)]
+REGISTER += [("xor", k, 1, TILE[k] + 16, TILE[k]) for k in (2, 3, 6, 10)]
+REGISTER += [("rs-legacy", k, m, TILE[k] + 16, TILE[k]) for k, m in ((3, 2), (6, 3), (10, 4))]
+# The byte kernel: k = 5 is not a shape of the register kernel, so this case
+# has always run gf_scrub_bytes (the other byte-kernel cases are the
+# test_generic_* below and test_gpu_scrub_variants.py)
+BYTE = [("xor", 5, 1, 4112, 4096)]
+FAST = REGISTER + BYTE
 IDS = [f"{c}-{k}-{m}-{cell}" for c, k, m, cell, _ in FAST]
+assert len(set(IDS)) == len(IDS) == 6 + 16 + 4 + 3 + 1
 
 
 @pytest.fixture(scope="module")
@@ -45,18 +93,25 @@ def coder(k, m, codec="rs"):
 _truth = {}
 
 
+def consistent_stripes(codec, k, m, stripes, cell):
+    """A fresh, writable [stripes, k+m, cell]: random data and the oracle's
+    parity rows applied to it (the same bytes for the same arguments)."""
+    rng = np.random.default_rng(104729 * k + 31 * m + stripes + cell + len(codec))
+    t = np.empty((stripes, k + m, cell), dtype=np.uint8)
+    t[:, :k] = rng.integers(0, 256, size=(stripes, k, cell), dtype=np.uint8)
+    flat = [np.ascontiguousarray(t[:, i]).reshape(-1) for i in range(k)]
+    par = O.matmul_shards(O.codec_matrix(codec, k, m)[k:], flat)
+    for j in range(m):
+        t[:, k + j] = par[j].reshape(stripes, cell)
+    return t
+
+
 def truth(codec, k, m, stripes, cell):
-    """Consistent stripes [stripes, k+m, cell] (computed once per shape, shared,
-    read-only): random data and the oracle's parity rows applied to it."""
+    """Consistent stripes [stripes, k+m, cell], computed once per shape,
+    shared, read-only."""
     key = (codec, k, m, stripes, cell)
     if key not in _truth:
-        rng = np.random.default_rng(104729 * k + 31 * m + stripes + cell + len(codec))
-        t = np.empty((stripes, k + m, cell), dtype=np.uint8)
-        t[:, :k] = rng.integers(0, 256, size=(stripes, k, cell), dtype=np.uint8)
-        flat = [np.ascontiguousarray(t[:, i]).reshape(-1) for i in range(k)]
-        par = O.matmul_shards(O.codec_matrix(codec, k, m)[k:], flat)
-        for j in range(m):
-            t[:, k + j] = par[j].reshape(stripes, cell)
+        t = consistent_stripes(codec, k, m, stripes, cell)
         t.setflags(write=False)
         _truth[key] = t
     return _truth[key]
