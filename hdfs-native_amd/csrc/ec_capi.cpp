@@ -34,6 +34,7 @@
 #include "checksum.hpp"
 #include "checksum_tables.hpp"
 #include "ec_kernels.hpp"
+#include "ec_reconstruct_crc.hpp"
 #include "gf256.hpp"
 #include "host_gf.hpp"
 #include "jit.hpp"
@@ -890,6 +891,28 @@ size_t hec_decode_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
 
 namespace {
 
+// The next of the coder's two pinned staging images (c->mixed_host[*b]) with
+// room for `need` bytes, free for reuse: its last upload has run.  The caller
+// holds c->mixed_mu, fills the image, enqueues the copy and records
+// c->ev_mixed[*b] behind it.
+int pinned_image(hec_coder* c, size_t need, int* b_out) {
+    const int b = c->mixed_next;
+    c->mixed_next ^= 1;
+    *b_out = b;
+    if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
+    else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
+    if (c->mixed_host_bytes[b] < need) {
+        if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
+        c->mixed_host[b] = nullptr;
+        c->mixed_host_bytes[b] = 0;
+        const size_t grow = std::max(need, 2 * c->mixed_host_bytes[b ^ 1]);
+        HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), grow, hipHostMallocDefault),
+                HEC_ERR_NO_MEMORY);
+        c->mixed_host_bytes[b] = grow;
+    }
+    return HEC_OK;
+}
+
 // Body of hec_decode_device_mixed.  Shards that no stripe's plan reads may be
 // null here (the verified read's phase 2); the public call requires storage
 // for every shard index.
@@ -983,19 +1006,9 @@ int mixed_decode_impl(hec_coder* c, const uint8_t* const* d_shards, const size_t
         {
             // one of the coder's two pinned images, free once its last copy has run
             std::lock_guard<std::mutex> lk(c->mixed_mu);
-            const int b = c->mixed_next;
-            c->mixed_next ^= 1;
-            if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
-            else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
-            if (c->mixed_host_bytes[b] < need) {
-                if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
-                c->mixed_host[b] = nullptr;
-                c->mixed_host_bytes[b] = 0;
-                const size_t want = std::max(need, 2 * c->mixed_host_bytes[b ^ 1]);
-                HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), want, hipHostMallocDefault),
-                        HEC_ERR_NO_MEMORY);
-                c->mixed_host_bytes[b] = want;
-            }
+            int b;
+            const int irc = pinned_image(c, need, &b);
+            if (irc != HEC_OK) return irc;
             uint8_t* host = c->mixed_host[b];
             uint32_t* soff = reinterpret_cast<uint32_t*>(host);
             for (size_t s_ = 0; s_ < stripes; s_++)
@@ -1324,19 +1337,9 @@ int mixed_reconstruct_impl(hec_coder* c, const uint8_t* const* d_shards, const s
         // one of the coder's two pinned images (shared with the mixed decode),
         // free once its last copy has run
         std::lock_guard<std::mutex> lk(c->mixed_mu);
-        const int b = c->mixed_next;
-        c->mixed_next ^= 1;
-        if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
-        else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
-        if (c->mixed_host_bytes[b] < need) {
-            if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
-            c->mixed_host[b] = nullptr;
-            c->mixed_host_bytes[b] = 0;
-            const size_t grow = std::max(need, 2 * c->mixed_host_bytes[b ^ 1]);
-            HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), grow, hipHostMallocDefault),
-                    HEC_ERR_NO_MEMORY);
-            c->mixed_host_bytes[b] = grow;
-        }
+        int b;
+        const int irc = pinned_image(c, need, &b);
+        if (irc != HEC_OK) return irc;
         uint8_t* host = c->mixed_host[b];
         uint32_t* soff = reinterpret_cast<uint32_t*>(host);
         for (size_t s_ = 0; s_ < stripes; s_++)
@@ -2263,6 +2266,307 @@ int hec_decode_verify_device(hec_coder_t* c, int checksum_type, const uint8_t* c
         }
         HEC_HIP(hipStreamSynchronize(stream), HEC_ERR_DEVICE);
         return status;
+    });
+}
+
+// ---- verified reconstruction: chunk checksums in and out ---------------------
+// hec_reconstruct_crc_device*: the reconstruct calls with the survivors' chunk
+// sums verified and the rebuilt units' written in the same pass
+// (ec_reconstruct_crc.hip), or as a composition of internal launches where
+// the fused kernel does not take the shape.
+
+namespace {
+
+// One uniform group of stripes of a verified reconstruction: a plan, its
+// target rows, and (mixed form) the device list of the group's stripes.
+struct CrcGroupCall {
+    const DecodePlan* plan;
+    const std::vector<size_t>* rows;
+    size_t stripes;            // stripes of the group (entries of d_list)
+    const uint32_t* d_list;    // null: stripes 0 .. stripes-1
+};
+
+// What every entry point checks the same way; kind < 0 = HEC_CHECKSUM_NULL.
+int recon_crc_check(const hec_coder* c, int checksum_type, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                    const uint8_t* d_bad, const uint8_t* d_sums, int* kind) {
+    if (!c || cell_len == 0) return HEC_ERR_INVALID_ARG;
+    *kind = -1;
+    if (checksum_type == HEC_CHECKSUM_NULL) return HEC_OK;
+    *kind = crc_kind(checksum_type);
+    if (*kind < 0 || bpc == 0 || !d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
+        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// The shapes gf_reconstruct_crc takes (launch_reconstruct_crc checks the
+// same): k, 512-B chunks, 16-B aligned cells.  The rows per plan and the
+// units' bases are checked per group.
+bool recon_crc_shape(const hec_coder* c, size_t cell_len, size_t bpc) {
+    return (c->k == 2 || c->k == 3 || c->k == 6 || c->k == 10) && bpc == 512 && cell_len % 16 == 0;
+}
+
+bool recon_crc_group_aligned(const hec_coder* c, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                             const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides) {
+    if (g.rows->size() > size_t(hec::kMaxR)) return false;
+    bool ok = true;
+    for (size_t r = 0; r < c->k; r++) {
+        const size_t u = g.plan->rec_survivors[r];
+        ok &= ((reinterpret_cast<uintptr_t>(d_shards[u]) | shard_strides[u]) & 15u) == 0;
+    }
+    for (size_t r : *g.rows) {
+        const size_t u = g.plan->lost[r];
+        ok &= ((reinterpret_cast<uintptr_t>(d_out[u]) | out_strides[u]) & 15u) == 0;
+    }
+    return ok;
+}
+
+// The fused launch of one group.  0 ok, -1 refused by the launcher, else HEC_*.
+int recon_crc_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                    const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides, size_t cell_len,
+                    const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
+    const size_t k = c->k, n = c->k + c->m;
+    const DecodePlan& p = *g.plan;
+    hec::MatmulArgs a;
+    std::memset(&a, 0, sizeof(a));
+    hec::ReconCrcArgs cs;
+    std::memset(&cs, 0, sizeof(cs));
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = p.rec_survivors[r];
+        a.in[r] = d_shards[u];
+        a.in_stride[r] = shard_strides[u];
+        cs.shard_id[r] = uint8_t(u);
+    }
+    for (size_t j = 0; j < g.rows->size(); j++) {
+        const size_t row = (*g.rows)[j], u = p.lost[row];
+        a.out[j] = d_out[u];
+        a.out_stride[j] = out_strides[u];
+        cs.shard_id[k + j] = uint8_t(u);
+        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+    }
+    a.k = int32_t(k);
+    a.r = int32_t(g.rows->size());
+    a.cell_len = cell_len;
+    a.stripes = g.stripes;
+    cs.sums = d_sums;
+    cs.expected = d_expected;
+    cs.bad = d_bad;
+    cs.n_total = uint32_t(n);
+    cs.kind = kind;
+    cs.stripe_list = g.d_list;
+    const int rc = hec::launch_reconstruct_crc(a, cs, c->device, stream);
+    if (rc <= 0) return rc;
+    return to_status(rc);
+}
+
+// Composition, first and last step: the survivors of a group verified
+// (verify = true) or its rebuilt units, read back from d_out, checksummed.
+int recon_crc_sums_pass(hec_coder* c, int kind, bool verify, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                        const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
+                        size_t cell_len, size_t bpc, const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums,
+                        hipStream_t stream) {
+    const size_t k = c->k, n = c->k + c->m;
+    const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t strides[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    uint8_t sid[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t cnt = 0;
+    if (verify) {
+        for (size_t r = 0; r < k; r++, cnt++) {
+            const size_t u = g.plan->rec_survivors[r];
+            bases[cnt] = d_shards[u];
+            strides[cnt] = shard_strides[u];
+            sid[cnt] = uint8_t(u);
+        }
+        return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, nullptr, d_expected,
+                               d_bad, stream, g.d_list);
+    }
+    for (size_t r : *g.rows) {
+        const size_t u = g.plan->lost[r];
+        bases[cnt] = d_out[u];
+        strides[cnt] = out_strides[u];
+        sid[cnt++] = uint8_t(u);
+    }
+    return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, d_sums, nullptr, nullptr,
+                           stream, g.d_list);
+}
+
+// [hec_reconstruct_device_mixed's workspace][stripe lists: u32 x stripes]
+size_t recon_crc_workspace(size_t k, size_t m, size_t stripes) {
+    return align_up(recon_workspace(k, m, stripes)) + align_up(stripes * sizeof(uint32_t));
+}
+
+// The stripe lists of a mixed call to the device through one of the coder's
+// two pinned images, as the mixed calls upload their plan offsets.
+int upload_stripe_lists(hec_coder* c, const std::vector<uint32_t>& flat, void* d_dst, hipStream_t stream) {
+    const size_t need = flat.size() * sizeof(uint32_t);
+    std::lock_guard<std::mutex> lk(c->mixed_mu);
+    int b;
+    const int irc = pinned_image(c, need, &b);
+    if (irc != HEC_OK) return irc;
+    std::memcpy(c->mixed_host[b], flat.data(), need);
+    HEC_HIP(hipMemcpyAsync(d_dst, c->mixed_host[b], need, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
+    HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
+    return HEC_OK;
+}
+
+}  // namespace
+
+int hec_reconstruct_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                               const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
+                               const uint8_t* want, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                               const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_device");
+    int kind;
+    const int chk = recon_crc_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    if (chk != HEC_OK) return chk;
+    if (kind < 0)
+        return hec_reconstruct_device(c, d_shards, shard_strides, d_out, out_strides, want, cell_len, stripes,
+                                      hip_stream);
+    if (!d_shards || !shard_strides) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        const size_t n = c->k + c->m;
+        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+        for (size_t i = 0; i < n; i++) present[i] = d_shards[i] != nullptr;
+        uint64_t want_mask;
+        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
+        const PlanRef p_ref = cached_plan(c, present);
+        const DecodePlan& p = *p_ref;
+        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
+        if (rows.empty() || stripes == 0) return HEC_OK;
+        if (p.rec_status != HEC_OK) return p.rec_status;
+        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
+        for (size_t r : rows)
+            if (!d_out[p.lost[r]]) return HEC_ERR_INVALID_ARG;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const CrcGroupCall call{&p, &rows, stripes, nullptr};
+        if (recon_crc_shape(c, cell_len, bytes_per_checksum) &&
+            recon_crc_group_aligned(c, call, d_shards, shard_strides, d_out, out_strides)) {
+            const int rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len,
+                                           d_expected, d_bad, d_sums, stream);
+            if (rc != -1) return rc;  // -1: refused, nothing launched
+        }
+        // the composition: verify the survivors, rebuild, checksum what was rebuilt
+        if (d_expected) {
+            const int rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides,
+                                               cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        const int rc = hec_reconstruct_device(c, d_shards, shard_strides, d_out, out_strides, want, cell_len, stripes,
+                                              hip_stream);
+        if (rc != HEC_OK) return rc;
+        return recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
+                                   bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+    });
+}
+
+size_t hec_reconstruct_crc_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return recon_crc_workspace(c->k, c->m, stripes);
+}
+
+int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                     const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
+                                     const uint64_t* present, const uint64_t* want, size_t cell_len, size_t stripes,
+                                     size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                     uint8_t* d_sums, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_device_mixed");
+    int kind;
+    const int chk = recon_crc_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    if (chk != HEC_OK) return chk;
+    if (kind < 0)
+        return hec_reconstruct_device_mixed(c, d_shards, shard_strides, d_out, out_strides, present, want, cell_len,
+                                            stripes, d_workspace, workspace_bytes, hip_stream);
+    if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;  // every unit needs storage (present in some stripe)
+    return guarded([&]() -> int {
+        const size_t k = c->k, m = c->m, n = k + m;
+        const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
+        // 1. the distinct (present, want) pairs with a target, each with its
+        // plan and the list of its stripes (host); fail before launching anything
+        struct Group {
+            ReconPlan rp;
+            std::vector<uint32_t> list;
+        };
+        std::map<std::pair<uint64_t, uint64_t>, size_t> ids;
+        std::vector<Group> groups;
+        uint64_t target_units = 0;
+        for (size_t s = 0; s < stripes; s++) {
+            const uint64_t mask = present[s] & all;
+            const uint64_t wmask = want ? (want[s] & all) : (all & ~mask);
+            if (wmask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+            if (!wmask) continue;
+            auto it = ids.find({mask, wmask});
+            if (it == ids.end()) {
+                uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+                for (size_t i = 0; i < n; i++) pres[i] = (mask >> i) & 1;
+                Group g;
+                g.rp.plan = cached_plan(c, pres);
+                if (g.rp.plan->rec_status != HEC_OK) return g.rp.plan->rec_status;
+                g.rp.rows = target_rows(*g.rp.plan, true, wmask);
+                target_units |= wmask;
+                it = ids.emplace(std::make_pair(mask, wmask), groups.size()).first;
+                groups.push_back(std::move(g));
+            }
+            groups[it->second].list.push_back(uint32_t(s));
+        }
+        if (groups.empty()) return HEC_OK;
+        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
+        for (size_t i = 0; i < n; i++)
+            if (((target_units >> i) & 1) && !d_out[i]) return HEC_ERR_INVALID_ARG;
+        // 2. the lists, flat, behind the plain mixed call's part of the workspace
+        const size_t lists_pos = align_up(recon_workspace(k, m, stripes));
+        std::vector<uint32_t> flat;
+        std::vector<size_t> off(groups.size());
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            off[gi] = flat.size();
+            flat.insert(flat.end(), groups[gi].list.begin(), groups[gi].list.end());
+        }
+        if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) ||
+            workspace_bytes < lists_pos + flat.size() * sizeof(uint32_t))
+            return HEC_ERR_INVALID_ARG;
+        const uint32_t* d_lists = reinterpret_cast<const uint32_t*>(static_cast<uint8_t*>(d_workspace) + lists_pos);
+        std::vector<CrcGroupCall> calls(groups.size());
+        bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum);
+        for (size_t gi = 0; gi < groups.size(); gi++) {
+            calls[gi] = CrcGroupCall{groups[gi].rp.plan.get(), &groups[gi].rp.rows, groups[gi].list.size(),
+                                     d_lists + off[gi]};
+            fused = fused && recon_crc_group_aligned(c, calls[gi], d_shards, shard_strides, d_out, out_strides);
+        }
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        int rc = upload_stripe_lists(c, flat, static_cast<uint8_t*>(d_workspace) + lists_pos, stream);
+        if (rc != HEC_OK) return rc;
+        // 3. one launch per pair ...
+        if (fused) {
+            for (const CrcGroupCall& call : calls) {
+                rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len, d_expected,
+                                     d_bad, d_sums, stream);
+                if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
+            }
+            return HEC_OK;
+        }
+        // ... or the composition: verify per pair, one plain mixed call, sums per pair
+        if (d_expected)
+            for (const CrcGroupCall& call : calls) {
+                rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides, cell_len,
+                                         bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                if (rc != HEC_OK) return rc;
+            }
+        rc = mixed_reconstruct_impl(c, d_shards, shard_strides, d_out, out_strides, present, want, cell_len, stripes,
+                                    d_workspace, lists_pos, hip_stream);
+        if (rc != HEC_OK) return rc;
+        for (const CrcGroupCall& call : calls) {
+            rc = recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
+                                     bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return HEC_OK;
     });
 }
 

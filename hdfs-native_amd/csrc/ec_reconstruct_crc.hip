@@ -1,0 +1,298 @@
+// ec_reconstruct_crc.hip -- reconstruction fused with the chunk checksums on
+// both sides of it, for the repair worker: the k survivors of a stripe arrive
+// with one CRC per 512-B chunk and are verified while the lost units are
+// rebuilt from the same registers (HDFS-15759: a silently bad survivor
+// poisons every rebuilt unit), and the rebuilt units leave with fresh chunk
+// sums (WritePacket::calculate_checksum, connection.rs:568-584) computed from
+// the registers that were just stored.  One pass of k reads + t writes where
+// verify + reconstruct + checksum make 2k reads + t writes + t reads.
+//
+// gf_reconstruct_crc is a sibling of gf_fused_crc's plain path
+// (ec_fused_kernel.hpp, the last branch of its tile loop): one input at a
+// time with the next one prefetched, the v_perm product tables of the launch's
+// coefficient rows, the fold checksum (scheme 12) over a wave-private 9-KiB
+// image of 144-B quarter rows, 256-thread blocks, two per CU.  It differs in
+// what is checksummed: the inputs only when VERIFY_IN (compared against the
+// expected sums), the outputs always (their sums stored), both addressed by
+// unit index in the engine's [stripe][k+m] layouts, and in an optional stripe
+// list, so a mixed batch takes one launch per distinct pattern.  Block tiles
+// in the fixed order: no counters, nothing to zero, capturable as is.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "ec_reconstruct_crc.hpp"
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"
+#include "ec_fused_kernel.hpp"
+#pragma clang diagnostic pop
+
+namespace hec {
+
+// K survivors, R target rows, SLABS KiB of every cell per wave-tile; a
+// checksum round is 64 quarters = 8 / SLABS cells' share.
+template <int K, int R, int SLABS, int KIND, bool VERIFY_IN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gf_reconstruct_crc(MatmulArgs a,
+                                                                                                      ReconCrcArgs cs) {
+    static_assert(SLABS == 4 || SLABS == 8, "one or two cells per checksum round");
+    static_assert(K > 0 && R >= 1 && R <= kMaxR, "compile-time k, 1..4 rows");
+    constexpr int SCHEME = 12;
+    using TL = crcdev::TableLayout<SCHEME>;
+    using Spec = crc::Spec<KIND>;
+    constexpr bool REFL = Spec::kReflected;
+    constexpr int BS = 256, WAVES = BS / 64;
+    constexpr int PITCH = 144, STAGE = 64 * PITCH, SPR = 8 / SLABS;
+    constexpr uint32_t WAVE_BYTES = SLABS * 1024u, TILE_BYTES = WAVES * WAVE_BYTES;
+    constexpr bool PF = R * SLABS <= 24;  // register prefetch of the next survivor
+    __shared__ PermTable s_tab[R][K];
+    __shared__ uint8_t s_exp[512];
+    __shared__ uint8_t s_log[256];
+    __shared__ uint8_t s_coef[R * kMaxK];
+    __shared__ uint32_t s_ctabs[TL::kWords];
+    __shared__ __attribute__((aligned(16))) uint8_t s_stage[WAVES * STAGE];
+    prologue<R, BS, K>(a, K, s_tab, s_exp, s_log, s_coef);
+    crcdev::stage_tables<SCHEME, BS>(s_ctabs, fused_tables<KIND>());
+    __syncthreads();
+    const uint32_t kfinal = fused_tables<KIND>().final512;
+
+    const uint64_t cell_len = a.cell_len;
+    const uint64_t nck = (cell_len + 511) / 512;  // checksum chunks per cell
+    const uint32_t total = a.total_tiles;
+    // the wave index as a scalar: byte offsets, unit bases and the stage
+    // pointer stay in SGPRs (saddr + 32-bit lane offset accesses)
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x / 64)), lane = threadIdx.x & 63;
+    // this lane's quarter in a round: row `lane` = piece lane/8 = (cell slot
+    // sir, slab), chunk half (lane/4)&1 of that slab, quarter qi
+    const int qi = lane & 3, piece = lane >> 3, sir = piece / SLABS, pslab = piece % SLABS, half = (lane >> 2) & 1;
+    uint8_t* stage = s_stage + wave * STAGE;
+    uint32_t* out_sums = reinterpret_cast<uint32_t*>(cs.sums);
+    const uint32_t* exp_sums = reinterpret_cast<const uint32_t*>(cs.expected);
+    const uint32_t wave_off = uint32_t(wave) * WAVE_BYTES;
+
+    for (uint32_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+        uint32_t lstripe, tcol;
+        tile_coords(tile, a, lstripe, tcol);
+        const uint64_t wbyte = uint64_t(tcol) * TILE_BYTES + wave_off;  // wave's first byte
+        if (wbyte >= cell_len) continue;  // wave-uniform
+        // the batch stripe of this launch stripe: addresses, sums and flags
+        const uint32_t stripe = cs.stripe_list ? cs.stripe_list[lstripe] : lstripe;
+        // dead slabs of a short last tile re-read offset 0 and never store
+        // (32-bit compare: see gf_fused_crc)
+        const uint64_t left = cell_len - wbyte;
+        const uint32_t left32 = left > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(left);
+        uint32_t voff[SLABS];
+        bool live[SLABS];
+#pragma unroll
+        for (int u = 0; u < SLABS; u++) {
+            const uint32_t o = uint32_t(u) * 1024u + uint32_t(lane) * 16u;
+            live[u] = o < left32;
+            voff[u] = live[u] ? o : 0u;
+        }
+        const uint64_t cbyte = wbyte + uint64_t(pslab) * 1024u + uint64_t(half) * 512u;
+        const bool in_cell = cbyte < cell_len;
+        const bool full = in_cell && cell_len - cbyte >= 512u;  // same for a chunk's 4 lanes
+
+        // The cell of this lane's quarter in a round whose slot 0 is unit
+        // shard_id[first] (`first` is a compile-time constant at every
+        // unrolled call site: scalar kernarg reads); slot 1 only exists when
+        // the round has two cells.
+        auto sum_cell = [&](int first, int count) {
+            const uint32_t sid = (SPR > 1 && sir > 0 && count > 1) ? cs.shard_id[first + 1] : cs.shard_id[first];
+            return uint64_t(stripe) * cs.n_total + sid;
+        };
+        // One round over the staged image: `count` cells starting at unit
+        // slot `first` of shard_id.  vin: survivors, compared against the
+        // expected sums; otherwise rebuilt units, their sums stored.
+        auto crc_round = [&](auto vin, int first, int count) {
+            constexpr bool VIN = decltype(vin)::value;
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+            const bool live_c = in_cell && sir < count;
+            uint32_t want = 0;
+            if (VIN && live_c && qi == 0)
+                want = exp_sums[sum_cell(first, count) * nck + cbyte / 512];  // issued before the lookups
+            uint32_t val = 0;
+            if (full && sir < count) {
+                uint32_t r = crcdev::quarter<SCHEME, REFL>(s_ctabs, stage + lane * PITCH, lane);
+                if (qi < 3) r = crcdev::shift_quarter<SCHEME>(s_ctabs, qi, r);
+                val = r;
+            } else if (live_c && qi == 0) {
+                // short last chunk of the cell: this lane walks it whole, bytewise
+                const uint32_t len = uint32_t(cell_len - cbyte);
+                uint32_t r = Spec::kInit;
+                for (uint32_t b = 0; b < len; b++)
+                    r = crcdev::byte_step<REFL, crcdev::ByteTable<SCHEME>::stride, crcdev::ByteTable<SCHEME>::bswap>(
+                        s_ctabs + crcdev::ByteTable<SCHEME>::off, r, stage[(lane + b / 128) * PITCH + (b % 128)]);
+                val = r ^ Spec::kXorout;
+            }
+            val ^= __shfl_xor(val, 1);
+            val ^= __shfl_xor(val, 2);
+            if (live_c && qi == 0) {
+                const uint32_t be = __builtin_bswap32(full ? (val ^ kfinal) : val);
+                if constexpr (VIN) {
+                    if (be != want) cs.bad[sum_cell(first, count)] = 1;
+                } else {
+                    out_sums[sum_cell(first, count) * nck + cbyte / 512] = be;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+        };
+        // slab u of the cell in round slot `slot`: lane l's 16 B -> row
+        // 8*(slot*SLABS + u) + l/8, byte 16*(l%8)
+        auto stage_piece = [&](int slot, int u, const u32x4& v) {
+            *reinterpret_cast<u32x4*>(stage + (8 * (slot * SLABS + u) + lane / 8) * PITCH + 16 * (lane % 8)) = v;
+        };
+        auto load_in = [&](int i, u32x4(&dst)[SLABS]) {
+#pragma unroll
+            for (int u = 0; u < SLABS; u++)
+                dst[u] = load16<true>(a.in[i] + (uint64_t(stripe) * a.in_stride[i] + wbyte) + voff[u]);
+        };
+
+        u32x4 acc[SLABS][R];
+#pragma unroll
+        for (int u = 0; u < SLABS; u++)
+#pragma unroll
+            for (int j = 0; j < R; j++) acc[u][j] = u32x4{0, 0, 0, 0};
+        u32x4 x[SLABS], xn[SLABS];
+        load_in(0, x);
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            if (PF && i + 1 < K) load_in(i + 1, xn);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (VERIFY_IN) {
+#pragma unroll
+                for (int u = 0; u < SLABS; u++) stage_piece(i % SPR, u, x[u]);
+            }
+            // opaque per-input table offset threaded through the accumulators:
+            // keeps the table reads (and the GF math) of input i from being
+            // hoisted next to those of the other inputs
+            uint32_t toff = uint32_t(i) * uint32_t(sizeof(PermTable));
+            asm volatile("" : "+v"(toff));
+#pragma unroll
+            for (int u = 0; u < SLABS; u++) {
+                asm volatile("" : "+v"(x[u]));
+#pragma unroll
+                for (int j = 0; j < R; j++) asm volatile("" : "+v"(acc[u][j]) : "v"(toff));
+            }
+            uint32_t tb[R][5];
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                const PermTable& t =
+                    *reinterpret_cast<const PermTable*>(reinterpret_cast<const char*>(&s_tab[j][0]) + toff);
+                tb[j][0] = t.t0lo;
+                tb[j][1] = t.t0hi;
+                tb[j][2] = t.t1lo;
+                tb[j][3] = t.t1hi;
+                tb[j][4] = t.t2;
+            }
+#pragma unroll
+            for (int u = 0; u < SLABS; u++)
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    const Sel sl = make_sel(x[u][d]);
+#pragma unroll
+                    for (int j = 0; j < R; j++)
+                        acc[u][j][d] ^= gf_mul4(tb[j][0], tb[j][1], tb[j][2], tb[j][3], tb[j][4], sl.s0, sl.s1, sl.s2);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (VERIFY_IN) {
+                // a round once its SPR survivors are staged, or at the last one
+                if (i % SPR == SPR - 1 || i == K - 1)
+                    crc_round(std::true_type{}, i - i % SPR, i % SPR + 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (i + 1 < K) {
+                if constexpr (PF) {
+#pragma unroll
+                    for (int u = 0; u < SLABS; u++) x[u] = xn[u];
+                } else {
+                    load_in(i + 1, x);
+                }
+            }
+        }
+        // the R rebuilt units: stored, staged, their sums written
+#pragma unroll
+        for (int j = 0; j < R; j++) {
+#pragma unroll
+            for (int u = 0; u < SLABS; u++) {
+                if (live[u])
+                    store16<true>(a.out[j] + (uint64_t(stripe) * a.out_stride[j] + wbyte) + voff[u], acc[u][j]);
+                stage_piece(j % SPR, u, acc[u][j]);
+            }
+            if (j % SPR == SPR - 1 || j == R - 1) crc_round(std::false_type{}, K + j - j % SPR, j % SPR + 1);
+        }
+    }
+}
+
+namespace {
+
+// SLABS by fused_slabs's rule (ec_fused.hip): 8 slabs per wave while the
+// r x 8 accumulators fit (k <= 6, r <= 3), else 4
+constexpr int recon_crc_slabs(int k, int r) { return (r <= 3 && k <= 6) ? 8 : 4; }
+
+template <int K, int R>
+const void* recon_crc_fn(int kind, bool verify_in) {
+    constexpr int SL = recon_crc_slabs(K, R);
+    if (kind == crc::kCrc32c)
+        return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, true>)
+                         : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, false>);
+    return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, true>)
+                     : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, false>);
+}
+
+template <int K>
+const void* recon_crc_pick_r(int r, int kind, bool verify_in) {
+    switch (r) {
+        case 1: return recon_crc_fn<K, 1>(kind, verify_in);
+        case 2: return recon_crc_fn<K, 2>(kind, verify_in);
+        case 3: return recon_crc_fn<K, 3>(kind, verify_in);
+        case 4: return recon_crc_fn<K, 4>(kind, verify_in);
+        default: return nullptr;
+    }
+}
+
+}  // namespace
+
+int launch_reconstruct_crc(const MatmulArgs& in, const ReconCrcArgs& cs, int device, hipStream_t stream) {
+    MatmulArgs a = in;
+    if (cs.kind != crc::kCrc32c && cs.kind != crc::kCksum) return -1;
+    if (a.r < 1 || a.r > kMaxR || a.cell_len % 16 != 0 || !cs.sums || (cs.expected && !cs.bad)) return -1;
+    if ((reinterpret_cast<uintptr_t>(cs.sums) | reinterpret_cast<uintptr_t>(cs.expected)) & 3u) return -1;
+    for (int i = 0; i < a.k; i++)
+        if (!a.in[i] || ((reinterpret_cast<uintptr_t>(a.in[i]) | a.in_stride[i]) & 15u)) return -1;
+    for (int j = 0; j < a.r; j++)
+        if (!a.out[j] || ((reinterpret_cast<uintptr_t>(a.out[j]) | a.out_stride[j]) & 15u)) return -1;
+    const bool verify_in = cs.expected != nullptr;
+    const void* fn = nullptr;
+    switch (a.k) {
+        case 2: fn = recon_crc_pick_r<2>(a.r, cs.kind, verify_in); break;
+        case 3: fn = recon_crc_pick_r<3>(a.r, cs.kind, verify_in); break;
+        case 6: fn = recon_crc_pick_r<6>(a.r, cs.kind, verify_in); break;
+        case 10: fn = recon_crc_pick_r<10>(a.r, cs.kind, verify_in); break;
+        default: break;
+    }
+    if (!fn) return -1;
+    const Tune tn = tune_snapshot();
+    const uint64_t chunks = a.cell_len / 16;
+    const uint64_t tile_bytes = 1024u * uint64_t(recon_crc_slabs(a.k, a.r)) * 4u;  // 4 waves x SLABS KiB
+    const uint64_t tps = (a.cell_len + tile_bytes - 1) / tile_bytes;
+    const uint64_t total = tps * a.stripes;
+    if (chunks > 0xFFFFFFFFull || total > 0xFFFFFFFFull || a.stripes > 0xFFFFFFFFull) return -1;
+    if (total == 0) return 0;
+    a.chunks = uint32_t(chunks);
+    a.tiles_per_stripe = uint32_t(tps);
+    a.total_tiles = uint32_t(total);
+    // groups of 8 stripes and 32 blocks per CU (2 resident), as launch_fused's
+    // block-tile case
+    tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 8u, a.group, a.grouped_tiles);
+    uint64_t grid = tn.grid ? uint64_t(tn.grid) : uint64_t(num_cus(device)) * 32;
+    if (grid > total) grid = total;
+    ReconCrcArgs c = cs;
+    void* args[] = {&a, &c};
+    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(256), args, 0, stream);
+    return e == hipSuccess ? 0 : int(e);
+}
+
+}  // namespace hec

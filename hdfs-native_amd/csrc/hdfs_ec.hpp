@@ -197,6 +197,55 @@ class Coder {
     }
     ScrubResult scrub_result(const hec_scrub_result_t& r) const { return make_result(r); }
 
+    // Verified reconstruction of a device-resident batch, asynchronous on
+    // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
+    // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and
+    // the rebuilt units' chunk sums written to d_sums ([stripe][k+m][nck]
+    // big-endian u32, at the targets' slots); with d_expected (same layout;
+    // may be d_sums) and d_bad ([stripe][k+m], zeroed by the caller) the
+    // survivors' sums are verified in the same pass.
+    void reconstruct_crc_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                const std::vector<size_t>& strides, const std::vector<uint8_t*>& d_out,
+                                const std::vector<size_t>& out_strides, const std::vector<size_t>* want,
+                                size_t cell_len, size_t stripes, size_t bytes_per_checksum, const uint8_t* d_expected,
+                                uint8_t* d_bad, uint8_t* d_sums, void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units || d_out.size() != units || out_strides.size() != units)
+            throw std::invalid_argument("reconstruct_crc_device: need data_units + parity_units slots");
+        std::vector<uint8_t> want_flags(units, 0);
+        if (want)
+            for (size_t t : *want) {
+                if (t >= units) throw std::invalid_argument("reconstruct_crc_device: want index out of range");
+                want_flags[t] = 1;
+            }
+        check(hec_reconstruct_crc_device(h_.get(), checksum_type, d_units.data(), strides.data(), d_out.data(),
+                                         out_strides.data(), want ? want_flags.data() : nullptr, cell_len, stripes,
+                                         bytes_per_checksum, d_expected, d_bad, d_sums, hip_stream));
+    }
+    // One pattern per stripe (hec_reconstruct_crc_device_mixed): present[s] bit
+    // i = unit i of stripe s is intact, want (nullptr = everything missing)
+    // bit t = rebuild unit t; d_workspace of reconstruct_crc_mixed_workspace_size
+    // (stripes) bytes, untouched until the stream has passed the call.
+    size_t reconstruct_crc_mixed_workspace_size(size_t stripes) const {
+        return hec_reconstruct_crc_mixed_workspace_size(h_.get(), stripes);
+    }
+    void reconstruct_crc_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                      const std::vector<size_t>& strides, const std::vector<uint8_t*>& d_out,
+                                      const std::vector<size_t>& out_strides, const std::vector<uint64_t>& present,
+                                      const std::vector<uint64_t>* want, size_t cell_len, size_t bytes_per_checksum,
+                                      const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, void* d_workspace,
+                                      size_t workspace_bytes, void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units || d_out.size() != units || out_strides.size() != units)
+            throw std::invalid_argument("reconstruct_crc_device_mixed: need data_units + parity_units slots");
+        if (want && want->size() != present.size())
+            throw std::invalid_argument("reconstruct_crc_device_mixed: one want mask per stripe");
+        check(hec_reconstruct_crc_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(), d_out.data(),
+                                               out_strides.data(), present.data(), want ? want->data() : nullptr,
+                                               cell_len, present.size(), bytes_per_checksum, d_expected, d_bad, d_sums,
+                                               d_workspace, workspace_bytes, hip_stream));
+    }
+
    private:
     ScrubResult make_result(const hec_scrub_result_t& r) const {
         ScrubResult s;

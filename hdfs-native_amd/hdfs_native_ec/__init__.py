@@ -64,6 +64,7 @@ EXPORTS = [
     "hec_encode_rows_workspace_size", "hec_encode_rows_device", "hec_decode_rows_host",
     "hec_reconstruct_plan", "hec_reconstruct", "hec_reconstruct_device",
     "hec_reconstruct_mixed_workspace_size", "hec_reconstruct_device_mixed",
+    "hec_reconstruct_crc_device", "hec_reconstruct_crc_mixed_workspace_size", "hec_reconstruct_crc_device_mixed",
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
 ]
 
@@ -183,6 +184,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_reconstruct_mixed_workspace_size": ([P, S], S),
         "hec_reconstruct_device_mixed": ([P, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64), S, S, P, S, P], I),
+        "hec_reconstruct_crc_device": ([P, I, PP, SP, PP, SP, P, S, S, S, P, P, P, P], I),
+        "hec_reconstruct_crc_mixed_workspace_size": ([P, S], S),
+        "hec_reconstruct_crc_device_mixed": ([P, I, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
         "hec_scrub_verdict": ([ctypes.c_uint64, ctypes.c_uint64, S, ctypes.POINTER(I)], I),
         "hec_scrub": ([P, PP, S, P], I),
         "hec_scrub_device": ([P, PP, SP, S, S, P, P], I),
@@ -631,6 +636,40 @@ class Coder:
                                                       wants, cell_len, stripes, ctypes.c_void_p(workspace_ptr),
                                                       workspace_bytes, ctypes.c_void_p(stream)))
 
+    def reconstruct_crc_device(self, shard_ptrs, shard_strides, out_ptrs, out_strides, cell_len, stripes, sums_ptr,
+                               want=None, expected_ptr=None, bad_ptr=None, bytes_per_checksum: int = 512,
+                               checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_reconstruct_crc_device: reconstruct_device with the rebuilt
+        units' chunk sums written to sums_ptr ([stripe][k+m][nck] big-endian
+        u32, at the targets' slots) and, with expected_ptr (same layout; may be
+        sums_ptr) and bad_ptr ([stripe][k+m] flags, zeroed by the caller), the
+        survivors' sums verified in the same pass."""
+        _check(self._lib.hec_reconstruct_crc_device(self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]),
+                                                    _sp(shard_strides), _pp([p or 0 for p in out_ptrs]),
+                                                    _sp(out_strides), _want_bytes(len(shard_ptrs), want), cell_len,
+                                                    stripes, bytes_per_checksum, ctypes.c_void_p(expected_ptr),
+                                                    ctypes.c_void_p(bad_ptr), ctypes.c_void_p(sums_ptr),
+                                                    ctypes.c_void_p(stream)))
+
+    def reconstruct_crc_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_reconstruct_crc_mixed_workspace_size(self._h, stripes)
+
+    def reconstruct_crc_device_mixed(self, shard_ptrs, shard_strides, out_ptrs, out_strides, present_masks,
+                                     want_masks, cell_len, stripes, sums_ptr, workspace_ptr, workspace_bytes,
+                                     expected_ptr=None, bad_ptr=None, bytes_per_checksum: int = 512,
+                                     checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_reconstruct_crc_device_mixed: reconstruct_device_mixed with the
+        checksum buffers of reconstruct_crc_device; the workspace is
+        reconstruct_crc_mixed_workspace_size(stripes) bytes."""
+        masks = (ctypes.c_uint64 * stripes)(*present_masks)
+        wants = None if want_masks is None else (ctypes.c_uint64 * stripes)(*want_masks)
+        _check(self._lib.hec_reconstruct_crc_device_mixed(self._h, checksum_type, _pp(shard_ptrs), _sp(shard_strides),
+                                                          _pp([p or 0 for p in out_ptrs]), _sp(out_strides), masks,
+                                                          wants, cell_len, stripes, bytes_per_checksum,
+                                                          ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+                                                          ctypes.c_void_p(sums_ptr), ctypes.c_void_p(workspace_ptr),
+                                                          workspace_bytes, ctypes.c_void_p(stream)))
+
     def gf_matmul_device(self, matrix: List[List[int]], in_ptrs, in_strides, out_ptrs, out_strides, cell_len,
                          stripes, stream: int = 0) -> None:
         rows, cols = len(matrix), len(matrix[0])
@@ -814,6 +853,33 @@ def reconstruct_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], w
     coder.reconstruct_device_mixed(ptrs, strides, ptrs, strides, list(present_masks),
                                    None if want_masks is None else list(want_masks), cells.shape[2], S,
                                    workspace.data_ptr(), workspace.numel(), s.cuda_stream)
+    return workspace
+
+
+def reconstruct_crc_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], sums, want_masks=None,
+                                expected=None, bad=None, checksum_type: int = CHECKSUM_CRC32C, stream=None,
+                                workspace=None):
+    """reconstruct_batch_mixed with the chunk checksums in the same pass:
+    sums is a cuda tensor of S * (k+m) * ceil(cell / 512) 4-byte words (int32
+    or 4 uint8 each; big-endian sums) that receives the rebuilt units' chunk
+    sums at their own slots; expected (same layout, may be `sums` itself) and
+    bad (uint8 [S, k+m], zeroed by the caller) make the call verify the
+    survivors every stripe's plan reads, flagging a mismatch in bad.  Returns
+    the workspace (reusable once the stream has passed the call)."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    nbytes = coder.reconstruct_crc_mixed_workspace_size(S)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=cells.device)
+    coder.reconstruct_crc_device_mixed(ptrs, strides, ptrs, strides, list(present_masks),
+                                       None if want_masks is None else list(want_masks), cells.shape[2], S,
+                                       sums.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       expected_ptr=None if expected is None else expected.data_ptr(),
+                                       bad_ptr=None if bad is None else bad.data_ptr(),
+                                       checksum_type=checksum_type, stream=s.cuda_stream)
     return workspace
 
 

@@ -299,6 +299,69 @@ int hec_reconstruct_device_mixed(hec_coder_t *coder, const uint8_t *const *d_sha
                                  size_t cell_len, size_t stripes, void *d_workspace, size_t workspace_bytes,
                                  void *hip_stream);
 
+/* Verified reconstruction: the two device calls above with the chunk
+ * checksums that surround a repair worker's bytes, in the same pass over the
+ * cells.  The k survivors arrive from DataNodes with one sum per
+ * bytes_per_checksum chunk and are verified before anything is trusted that
+ * was rebuilt from them (HDFS-15759); the rebuilt units leave as packets that
+ * need fresh chunk sums (WritePacket::calculate_checksum,
+ * connection.rs:568-584).  Shards, outputs, want, present, survivors (the
+ * first k present units), plans, in-place repair (d_out[t] may be the lost
+ * slot) and status codes are exactly those of hec_reconstruct_device /
+ * hec_reconstruct_device_mixed.
+ *   d_sums, d_expected: [stripe][k+m][nck] big-endian u32, nck =
+ *     ceil(cell_len / bytes_per_checksum); d_bad: [stripe][k+m] bytes -- the
+ *     layouts of hec_encode_crc_device / hec_decode_verify_device; the sums
+ *     buffers 4-byte aligned.
+ *   d_sums (required) receives the chunk sums of every rebuilt unit at that
+ *     unit's own slot; no other word of it is written.
+ *   d_expected (optional; requires d_bad): the k survivors a stripe's plan
+ *     reads are verified against it; a mismatch sets d_bad[s*(k+m) + unit] =
+ *     1.  Flags are only ever set: the caller zeroes them, as for
+ *     hec_checksum_verify_device.  Present units the plan does not read are
+ *     not verified.  d_expected == d_sums is allowed (survivor slots are read,
+ *     target slots written, and they are disjoint): a worker keeps one sums
+ *     array per batch and the call fills in the holes.
+ * Both calls are asynchronous on hip_stream: they never synchronise with the
+ * device, never allocate device memory and never read the flags back.  A
+ * stripe with a flagged survivor still gets its targets and their sums
+ * written, with unspecified content: the caller reads d_bad, clears those
+ * bits in `present`, may add the bad unit to `want`, and calls the mixed form
+ * again for those stripes (want = 0 for every other stripe).
+ * HEC_CHECKSUM_NULL runs the plain reconstruct call and ignores the three
+ * checksum buffers; HEC_CHECKSUM_CRC32C and HEC_CHECKSUM_CRC32 are supported.
+ * HEC_ERR_DEVICE on a host-only coder.  HEC_ERR_INVALID_ARG, nothing queued:
+ * NULL coder, cell_len == 0, bytes_per_checksum == 0, NULL or misaligned
+ * d_sums, d_expected without d_bad.  HEC_OK, nothing queued: stripes == 0 or
+ * no target anywhere.
+ * One fused kernel (reads k cells, writes t cells and their sums) for k in
+ * {2,3,6,10}, at most 4 target rows per pattern, bytes_per_checksum == 512 and
+ * 16-B aligned bases, strides and cell_len; everything else runs, in stream
+ * order, a verify pass over the survivors (with d_expected), the plain
+ * reconstruct call and a checksum pass over the rebuilt units read back from
+ * d_out: the same results.
+ * The mixed form takes one launch per distinct (present, want) pair, each
+ * over a device list of that pair's stripes -- at most k+m launches after one
+ * node failure.  The lists sit in d_workspace behind what
+ * hec_reconstruct_device_mixed keeps there
+ * (hec_reconstruct_crc_mixed_workspace_size bytes, 4-byte aligned, always
+ * required; untouched until the stream reaches the work; calls in flight at
+ * once need different workspaces). */
+int hec_reconstruct_crc_device(hec_coder_t *coder, int checksum_type,
+                               const uint8_t *const *d_shards, const size_t *shard_strides,
+                               uint8_t *const *d_out, const size_t *out_strides, const uint8_t *want,
+                               size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                               const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums, void *hip_stream);
+
+size_t hec_reconstruct_crc_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+int hec_reconstruct_crc_device_mixed(hec_coder_t *coder, int checksum_type,
+                                     const uint8_t *const *d_shards, const size_t *shard_strides,
+                                     uint8_t *const *d_out, const size_t *out_strides,
+                                     const uint64_t *present, const uint64_t *want,
+                                     size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                     const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums,
+                                     void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ---- Scrub: verify a stripe's parity and locate a corrupt unit ----------- *
  * What a block scanner or a repair worker asks before and after it rebuilds
  * (`hdfs debug verifyEC`; dfs.datanode.ec.reconstruct.validation, HDFS-15759):

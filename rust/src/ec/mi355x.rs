@@ -99,6 +99,19 @@ unsafe extern "C" {
                                     d_out: *const *mut u8, out_strides: *const usize, present: *const u64,
                                     want: *const u64, cell_len: usize, stripes: usize, d_workspace: *mut c_void,
                                     workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_crc_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                  shard_strides: *const usize, d_out: *const *mut u8, out_strides: *const usize,
+                                  want: *const u8, cell_len: usize, stripes: usize, bytes_per_checksum: usize,
+                                  d_expected: *const u8, d_bad: *mut u8, d_sums: *mut u8,
+                                  stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_crc_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_reconstruct_crc_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                        shard_strides: *const usize, d_out: *const *mut u8,
+                                        out_strides: *const usize, present: *const u64, want: *const u64,
+                                        cell_len: usize, stripes: usize, bytes_per_checksum: usize,
+                                        d_expected: *const u8, d_bad: *mut u8, d_sums: *mut u8,
+                                        d_workspace: *mut c_void, workspace_bytes: usize,
+                                        stream: *mut c_void) -> c_int;
     fn hec_scrub_verdict(ruled_out: u64, bad_bytes: u64, units: usize, unit: *mut c_int) -> c_int;
     fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
     fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
@@ -300,6 +313,74 @@ impl GpuCoder {
                                          out_strides.as_ptr(), present.as_ptr(),
                                          want.map_or(std::ptr::null(), |w| w.as_ptr()), cell, present.len(),
                                          workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// `reconstruct_device` with the chunk checksums that surround a repair
+    /// worker's bytes, in the same pass (`hec_reconstruct_crc_device`).  `sums`
+    /// (`[stripe][k+m][nck]` big-endian u32, 4-byte aligned) receives the chunk
+    /// sums of every rebuilt unit at that unit's own slot and nothing else.
+    /// With `expected` (same layout; may be `sums` itself) and `bad`
+    /// (`[stripe][k+m]` bytes the caller zeroed) the k survivors the plan reads
+    /// are verified and a mismatch sets `bad[s * (k+m) + unit] = 1`; pass null
+    /// for both when the survivors' sums are already trusted.  `checksum_type`
+    /// is a `ChecksumTypeProto` value (CRC32C or CRC32; NULL = plain
+    /// `reconstruct_device`).  Never blocks: read `bad` back once `stream` has
+    /// passed the call.
+    ///
+    /// # Safety
+    /// As `encode_device`; the checksum buffers valid for their layouts on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_crc_device(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                         out: &[*mut u8], out_strides: &[usize], want: Option<&[usize]>,
+                                         cell: usize, stripes: usize, bytes_per_checksum: usize,
+                                         expected: *const u8, bad: *mut u8, sums: *mut u8,
+                                         stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        let flags = want.map(|w| want_flags(n, w));
+        check(unsafe {
+            hec_reconstruct_crc_device(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
+                                       out.as_ptr(), out_strides.as_ptr(),
+                                       flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()), cell, stripes,
+                                       bytes_per_checksum, expected, bad, sums, stream)
+        })
+    }
+
+    /// Device bytes `reconstruct_crc_device_mixed` needs for `stripes` stripes.
+    pub fn reconstruct_crc_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_reconstruct_crc_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// A repair batch with its checksums (`hec_reconstruct_crc_device_mixed`):
+    /// `reconstruct_device_mixed` plus the checksum buffers of
+    /// `reconstruct_crc_device`.  A stripe whose survivor is flagged in `bad`
+    /// is repaired by a second call for those stripes alone: clear the bad
+    /// unit's bit in `present`, add it to `want` if it should be rebuilt too,
+    /// and pass `want = 0` for every other stripe.  `workspace` is device memory
+    /// of `reconstruct_crc_mixed_workspace_size(stripes)` bytes, untouched until
+    /// `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `reconstruct_crc_device`; `workspace` valid for `workspace_bytes` on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_crc_device_mixed(&self, checksum_type: i32, shards: &[*const u8],
+                                               shard_strides: &[usize], out: &[*mut u8], out_strides: &[usize],
+                                               present: &[u64], want: Option<&[u64]>, cell: usize,
+                                               bytes_per_checksum: usize, expected: *const u8, bad: *mut u8,
+                                               sums: *mut u8, workspace: *mut c_void, workspace_bytes: usize,
+                                               stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        assert!(want.map_or(true, |w| w.len() == present.len()), "one want mask per stripe");
+        check(unsafe {
+            hec_reconstruct_crc_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(),
+                                             shard_strides.as_ptr(), out.as_ptr(), out_strides.as_ptr(),
+                                             present.as_ptr(), want.map_or(std::ptr::null(), |w| w.as_ptr()), cell,
+                                             present.len(), bytes_per_checksum, expected, bad, sums, workspace,
+                                             workspace_bytes, stream)
         })
     }
 
