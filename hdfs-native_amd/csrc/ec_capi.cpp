@@ -1475,6 +1475,297 @@ int hec_scrub_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_
     });
 }
 
+// ---- degraded scrub: one presence mask per stripe ---------------------------
+
+namespace {
+
+// The check plan of a presence mask: S = the first k present units, E = the
+// other present units, and the rows of G = C[E] . inverse(C[S]) -- the cached
+// reconstruction plan of `present = S only` with the units of E wanted.
+struct ScrubPlan {
+    PlanRef plan;              // rec_survivors = S; lost = every unit outside S
+    std::vector<size_t> rows;  // positions of E in plan->lost, ascending
+    uint64_t missing = 0;      // units the mask lacks
+};
+
+// False when the mask has no extra (e == 0: exactly k present, or fewer).
+// A plan that could not be built leaves its status in sp->plan->rec_status.
+bool scrub_plan_of(hec_coder* c, uint64_t mask, ScrubPlan* sp) {
+    const size_t k = c->k, n = c->k + c->m;
+    uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS] = {0};
+    uint64_t emask = 0;
+    size_t seen = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!((mask >> i) & 1)) continue;
+        if (seen < k) pres[i] = 1;
+        else emask |= uint64_t(1) << i;
+        seen++;
+    }
+    if (seen <= k) return false;
+    sp->plan = cached_plan(c, pres);
+    sp->rows = target_rows(*sp->plan, true, emask);
+    sp->missing = ~mask & ((uint64_t(1) << n) - 1);  // n <= 48
+    return true;
+}
+
+// The plan's positions (bit i < k survivor i, bit k + j extra j) as unit indices.
+uint64_t scrub_positions_to_units(const ScrubPlan& sp, size_t k, uint64_t pos) {
+    uint64_t units = 0;
+    for (size_t i = 0; i < k; i++)
+        if ((pos >> i) & 1) units |= uint64_t(1) << sp.plan->rec_survivors[i];
+    for (size_t j = 0; j < sp.rows.size(); j++)
+        if ((pos >> (k + j)) & 1) units |= uint64_t(1) << sp.plan->lost[sp.rows[j]];
+    return units;
+}
+
+// Plans of a batch: every presence mask with at least one extra, that is with
+// fewer than m units missing, capped by the stripe count.
+size_t max_scrub_plans(size_t k, size_t m, size_t stripes) {
+    double total = 0, c = 1;
+    for (size_t j = 0; j < m; j++) {
+        total += c;  // C(k+m, j)
+        if (total >= double(stripes)) return stripes;
+        c = c * double(k + m - j) / double(j + 1);
+    }
+    return std::min(stripes, size_t(total));
+}
+
+// A plan's blob: header + e x k PermTables (register kernel) or coefficient
+// bytes padded to 16 B (byte kernel).
+size_t scrub_plan_bytes(size_t k, size_t e, bool tables) {
+    return sizeof(hec::ScrubPlanHeader) + (tables ? e * k * sizeof(hec::PermTable) : ((e * k + 15) & ~size_t(15)));
+}
+
+bool scrub_fast_k(size_t k) { return k == 2 || k == 3 || k == 6 || k == 10; }
+
+// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters]
+// (hec::ScrubMixedArgs), sized for the worst batch of `stripes` masks.
+size_t scrub_workspace(size_t k, size_t m, size_t stripes) {
+    size_t per = scrub_plan_bytes(k, m, false);
+    if (scrub_fast_k(k)) per = std::max(per, scrub_plan_bytes(k, std::min(m, size_t(hec::kMaxR)), true));
+    return align_up(align_up(stripes * sizeof(uint32_t)) + max_scrub_plans(k, m, stripes) * per) +
+           size_t(hec::kMixedQueues) * hec::kMixedQueueStride;
+}
+
+}  // namespace
+
+int hec_scrub_plan(const char* codec, size_t data_units, size_t parity_units, const uint8_t* present, size_t* n_checks,
+                   size_t* survivors, size_t* extras, uint8_t* matrix) {
+    if (!present || !n_checks || data_units == 0 || parity_units == 0 || data_units + parity_units > 64)
+        return HEC_ERR_INVALID_ARG;
+    const std::string name = codec ? codec : "rs";
+    if (name != "rs" && name != "xor" && name != "rs-legacy") return HEC_ERR_UNSUPPORTED_CODEC;
+    if (name == "xor" && parity_units != 1) return HEC_ERR_INVALID_ARG;
+    const size_t k = data_units, n = data_units + parity_units;
+    return guarded([&] {
+        std::vector<uint8_t> pres(n, 0);
+        uint64_t emask = 0;
+        size_t seen = 0;
+        for (size_t i = 0; i < n; i++) {
+            if (!present[i]) continue;
+            if (seen < k) pres[i] = 1;
+            else emask |= uint64_t(1) << i;
+            seen++;
+        }
+        *n_checks = seen > k ? seen - k : 0;
+        if (seen <= k) return int(HEC_OK);  // nothing to check against
+        const std::vector<uint8_t> enc = name == "xor"         ? hec::gen_xor_matrix(data_units)
+                                         : name == "rs-legacy" ? hec::gen_rs_legacy_matrix(data_units, parity_units)
+                                                               : hec::gen_rs_matrix(data_units, parity_units);
+        const DecodePlan p = compute_plan(data_units, parity_units, pres.data(), enc);
+        if (p.rec_status != HEC_OK) return p.rec_status;
+        const std::vector<size_t> rows = target_rows(p, true, emask);
+        if (survivors) std::copy(p.rec_survivors.begin(), p.rec_survivors.end(), survivors);
+        for (size_t t = 0; t < rows.size(); t++) {
+            if (extras) extras[t] = p.lost[rows[t]];
+            if (matrix) std::memcpy(matrix + t * k, &p.rec_matrix[rows[t] * k], k);
+        }
+        return int(HEC_OK);
+    });
+}
+
+int hec_scrub_degraded(hec_coder_t* c, const uint8_t* const* shards, size_t shard_len, hec_scrub_result_t* out) {
+    if (!c || !shards || shard_len == 0 || !out) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t k = c->k, n = c->k + c->m;
+        out->ruled_out = out->bad_bytes = 0;
+        uint64_t mask = 0;
+        for (size_t i = 0; i < n; i++)
+            if (shards[i]) mask |= uint64_t(1) << i;
+        ScrubPlan sp;
+        if (!scrub_plan_of(c, mask, &sp)) return int(HEC_OK);  // e == 0: unchecked, nothing read
+        if (sp.plan->rec_status != HEC_OK) return sp.plan->rec_status;
+        Targets t;
+        gather_targets(*sp.plan, k, sp.rows, t);
+        // the host routine over the permuted unit list [S..., E...] with G in
+        // the place of P; its bits are positions of that list
+        const uint8_t* units[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+        for (size_t i = 0; i < k; i++) units[i] = shards[sp.plan->rec_survivors[i]];
+        for (size_t j = 0; j < t.units.size(); j++) units[k + j] = shards[t.units[j]];
+        uint64_t pos = 0, bad = 0;
+        hec::host::scrub(hec::host::best_isa(), t.matrix, t.aff, k, t.units.size(), units, shard_len, &pos, &bad);
+        out->bad_bytes = bad;
+        out->ruled_out = bad ? (scrub_positions_to_units(sp, k, pos) | sp.missing) : 0;
+        return int(HEC_OK);
+    });
+}
+
+size_t hec_scrub_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return scrub_workspace(c->k, c->m, stripes);
+}
+
+int hec_scrub_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                           const uint64_t* present, size_t cell_len, size_t stripes, hec_scrub_result_t* d_results,
+                           void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_device_mixed");
+    if (!c || !d_shards || !shard_strides || !present || cell_len == 0 || !d_results ||
+        (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0)
+        return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;  // every unit needs storage (present in some stripe)
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t k = c->k, n = c->k + c->m;
+        const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
+        // 1. plan per distinct mask (host); fail before anything is queued
+        constexpr uint32_t kUnchecked = 0xFFFFFFFFu;
+        std::unordered_map<uint64_t, uint32_t> ids;
+        std::vector<ScrubPlan> plans;
+        std::vector<uint32_t> stripe_plan(stripes);
+        size_t max_e = 0;
+        bool pivots = true;  // row 0 of every plan without a zero
+        for (size_t s = 0; s < stripes; s++) {
+            const uint64_t mask = present[s] & all;
+            auto it = ids.find(mask);
+            if (it == ids.end()) {
+                uint32_t id = kUnchecked;
+                ScrubPlan sp;
+                if (scrub_plan_of(c, mask, &sp)) {
+                    if (sp.plan->rec_status != HEC_OK) return sp.plan->rec_status;
+                    id = uint32_t(plans.size());
+                    max_e = std::max(max_e, sp.rows.size());
+                    const uint8_t* row0 = &sp.plan->rec_matrix[sp.rows[0] * k];
+                    for (size_t i = 0; i < k; i++) pivots &= row0[i] != 0;
+                    plans.push_back(std::move(sp));
+                }
+                it = ids.emplace(mask, id).first;
+            }
+            stripe_plan[s] = it->second;
+        }
+        const size_t need = scrub_workspace(k, c->m, stripes);
+        if (!plans.empty() && (!d_workspace || workspace_bytes < need ||
+                               (reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0))
+            return int(HEC_ERR_INVALID_ARG);
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        // the kernels only OR and add into the words: zeroed here, in stream order
+        HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        if (plans.empty()) return int(HEC_OK);  // no stripe can be checked
+
+        // 2. which kernel: the register kernel's shapes, else the byte kernel
+        bool fast = scrub_fast_k(k) && max_e <= size_t(hec::kMaxR) && pivots && cell_len % 16 == 0 &&
+                    cell_len <= 0xFFFFFFFFull;
+        for (size_t i = 0; fast && i < n; i++)
+            fast = ((reinterpret_cast<uintptr_t>(d_shards[i]) | shard_strides[i]) & 15u) == 0;
+        {
+            const uint64_t wave_tile = uint64_t(1024) * (k > 6 ? 2 : 4);  // bytes (ec_scrub_mixed.hip)
+            if (fast && ((cell_len + wave_tile - 1) / wave_tile) * stripes > 0xFFF00000ull) fast = false;
+        }
+
+        // 3. workspace image: per-stripe plan offsets | plan blobs | zeroed counters
+        const size_t blob_pos = align_up(stripes * sizeof(uint32_t));
+        size_t blob_bytes = 0;
+        std::vector<uint32_t> plan_off(plans.size());
+        for (size_t pi = 0; pi < plans.size(); pi++) {
+            plan_off[pi] = uint32_t(blob_bytes);
+            blob_bytes += scrub_plan_bytes(k, plans[pi].rows.size(), fast);
+        }
+        const size_t queue_pos = align_up(blob_pos + blob_bytes);
+        const size_t image = queue_pos + size_t(hec::kMixedQueues) * hec::kMixedQueueStride;  // <= need
+        {
+            // one of the coder's two pinned images (shared with the mixed
+            // decode and reconstruction), free once its last copy has run
+            std::lock_guard<std::mutex> lk(c->mixed_mu);
+            int b;
+            const int irc = pinned_image(c, image, &b);
+            if (irc != HEC_OK) return irc;
+            uint8_t* host = c->mixed_host[b];
+            uint32_t* soff = reinterpret_cast<uint32_t*>(host);
+            for (size_t s_ = 0; s_ < stripes; s_++)
+                soff[s_] = stripe_plan[s_] == kUnchecked ? hec::kNoPlan : plan_off[stripe_plan[s_]];
+            std::memset(host + stripes * sizeof(uint32_t), 0, image - stripes * sizeof(uint32_t));  // pads, counters
+            for (size_t pi = 0; pi < plans.size(); pi++) {
+                const DecodePlan& p = *plans[pi].plan;
+                const std::vector<size_t>& rows = plans[pi].rows;
+                uint8_t* at = host + blob_pos + plan_off[pi];
+                auto* hdr = reinterpret_cast<hec::ScrubPlanHeader*>(at);
+                hdr->e = uint32_t(rows.size());
+                for (size_t r = 0; r < k; r++) hdr->surv[r] = uint8_t(p.rec_survivors[r]);
+                hdr->missing_lo = uint32_t(plans[pi].missing);
+                hdr->missing_hi = uint32_t(plans[pi].missing >> 32);
+                uint8_t* body = at + sizeof(hec::ScrubPlanHeader);
+                for (size_t r = 0; r < rows.size(); r++) {
+                    hdr->extras[r] = uint8_t(p.lost[rows[r]]);
+                    if (fast)
+                        std::memcpy(body + r * k * sizeof(hec::PermTable), &p.rec_perm[rows[r] * k * 8],
+                                    k * sizeof(hec::PermTable));
+                    else
+                        std::memcpy(body + r * k, &p.rec_matrix[rows[r] * k], k);
+                }
+            }
+            HEC_HIP(hipMemcpyAsync(d_workspace, host, image, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
+            HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
+        }
+
+        // 4. launch
+        hec::ScrubMixedArgs a;
+        std::memset(&a, 0, sizeof(a));
+        for (size_t i = 0; i < n; i++) {
+            a.base[i] = d_shards[i];
+            a.stride[i] = shard_strides[i];
+        }
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
+        a.plans = ws + blob_pos;
+        a.blob_bytes = uint32_t(blob_bytes);
+        a.k = int32_t(k);
+        a.cell_len = cell_len;
+        a.stripes = stripes;
+        a.results = reinterpret_cast<uint64_t*>(d_results);
+        a.queue = reinterpret_cast<uint32_t*>(ws + queue_pos);
+        if (!fast) return to_status(hec::launch_scrub_mixed_bytes(a, c->device, stream));
+        if (hec::scrub_mixed_resident(stripes, blob_bytes)) {
+            const int rc = hec::launch_scrub_mixed(a, int(max_e), c->device, stream);
+            if (rc == 0) return int(HEC_OK);
+            if (rc != -1) return to_status(rc);
+            // refused (the runtime would not grant the LDS): per run below
+        }
+        // Plans past the resident LDS: the same kernel once per run of
+        // consecutive stripes sharing a plan, that one plan resident.
+        for (size_t s0 = 0; s0 < stripes;) {
+            size_t s1 = s0 + 1;
+            while (s1 < stripes && stripe_plan[s1] == stripe_plan[s0]) s1++;
+            if (stripe_plan[s0] != kUnchecked) {
+                hec::ScrubMixedArgs r = a;
+                for (size_t i = 0; i < n; i++) r.base[i] = d_shards[i] + s0 * shard_strides[i];
+                r.stripe_off = nullptr;
+                r.plans = ws + blob_pos + plan_off[stripe_plan[s0]];
+                r.blob_bytes = uint32_t(scrub_plan_bytes(k, plans[stripe_plan[s0]].rows.size(), true));
+                r.stripes = s1 - s0;
+                r.results = reinterpret_cast<uint64_t*>(d_results + s0);
+                r.queue = nullptr;
+                const int rc = hec::launch_scrub_mixed(r, int(plans[stripe_plan[s0]].rows.size()), c->device, stream);
+                if (rc != 0) return to_status(rc);
+            }
+            s0 = s1;
+        }
+        return int(HEC_OK);
+    });
+}
+
 // Pipelined pinned-host batch, 3 device slots and 3 streams:
 //   h2d stream:     [wait kernel(q-3) done: input slot free] H2D(q)  -> ev_in[slot]
 //   compute stream: [wait ev_in[slot], D2H(q-3) done: output slot free] encode(q) -> ev_k[slot]

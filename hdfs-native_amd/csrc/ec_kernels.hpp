@@ -187,6 +187,55 @@ struct ScrubArgs {
 // must already be zeroed in stream order.  0 ok, -1 invalid sizes, >0 hipError_t.
 int launch_scrub(const ScrubArgs& a, int device, hipStream_t stream);
 
+// ---- degraded scrub: one presence mask per stripe ---------------------------
+// Plan blob entry of gf_scrub_mixed / gf_scrub_mixed_bytes (ec_scrub_mixed.hip):
+// the stripe's survivors S (first k present units), extras E (the other
+// present units, ascending) and missing units, then the rows of
+// G = C[E] . inverse(C[S]): e x k PermTables (row j, survivor i at j*k + i) for
+// the register kernel, e x k coefficient bytes (padded to 16 B) for the byte
+// kernel.  Same size and leading fields as DevPlanHeader.
+struct ScrubPlanHeader {
+    uint32_t e;             // extras = checks of this stripe, >= 1
+    uint8_t surv[kMaxK];    // survivor unit indices
+    uint8_t extras[16];     // extra unit indices, ascending; 0 past e
+    uint32_t missing_lo;    // bit t set: unit t is missing (never the culprit)
+    uint32_t missing_hi;
+    uint8_t pad[4];
+};
+static_assert(sizeof(ScrubPlanHeader) == 64, "plan header is 64 B");
+
+// Workspace (device): [per-stripe plan offset: u32 x stripes][plan blob]
+// [kMixedQueueStride x kMixedQueues: the launch's zeroed tile counters].
+// Read-only over the present units; results as for ScrubArgs.
+struct ScrubMixedArgs {
+    const uint8_t* base[kMaxShards];  // all k+m unit bases, none null
+    uint64_t stride[kMaxShards];
+    const uint8_t* plans;             // blob: plan of stripe s at plans + stripe_off[s]
+    const uint32_t* stripe_off;       // per stripe; kNoPlan = not checkable (e == 0).  nullptr: the
+                                      // uniform plan -- every stripe of the launch uses the plan at `plans`
+    uint32_t blob_bytes;              // size of the blob (uniform: of the one plan)
+    int32_t k;
+    uint64_t cell_len;
+    uint64_t stripes;
+    uint64_t* results;                // [stripes][2], 8-B aligned, zeroed in stream order
+    uint32_t chunks, tiles_per_stripe, total_tiles, group, grouped_tiles;
+    uint32_t drain;                   // as MatmulArgs::drain
+    uint32_t* queue;                  // this launch's zeroed tile counters (nullptr: the fixed order)
+};
+
+// Register kernel, plans resident in LDS: k in {2,3,6,10}, every stripe's
+// e <= max_e <= kMaxR, 16-B aligned bases, strides and cell_len, row 0 of every
+// plan without a zero (the caller checks).  With a.stripe_off the batch's
+// offsets + blob must fit the resident budget (scrub_mixed_resident) and
+// a.queue is required; without it (uniform plan) the one plan at a.plans is
+// resident and the tiles go in the fixed order.  0 ok, -1 unsupported (nothing
+// was launched), >0 hipError_t.
+int launch_scrub_mixed(const ScrubMixedArgs& a, int max_e, int device, hipStream_t stream);
+bool scrub_mixed_resident(uint64_t stripes, uint64_t blob_bytes);
+// Byte-granular kernel: any k <= kMaxK, e <= 16, alignment and cell_len; plans
+// with coefficient bytes, read from global memory.  Same results.
+int launch_scrub_mixed_bytes(const ScrubMixedArgs& a, int device, hipStream_t stream);
+
 // True when the launch's coefficients are the RS coding matrix's parity rows
 // (gen_rs_matrix, gf256.rs:40-57) for its (k, r): the encode kernels then
 // run the bit-sliced XOR networks of xor_networks.hpp.

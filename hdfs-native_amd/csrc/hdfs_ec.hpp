@@ -197,6 +197,39 @@ class Coder {
     }
     ScrubResult scrub_result(const hec_scrub_result_t& r) const { return make_result(r); }
 
+    // Degraded scrub (hec_scrub_degraded): a stripe with missing units,
+    // nullopt = missing.  The missing units' bits are set in ruled_out once a
+    // position is bad; k units present or fewer cannot be checked: (0, 0).
+    ScrubResult scrub_degraded(const std::vector<std::optional<Bytes>>& units) const {
+        if (units.size() != k_ + m_) throw std::invalid_argument("scrub_degraded: need data_units + parity_units slots");
+        size_t n = 0;
+        std::vector<const uint8_t*> in(units.size(), nullptr);
+        for (size_t i = 0; i < units.size(); i++) {
+            if (!units[i]) continue;
+            if (n == 0) n = units[i]->size();
+            if (units[i]->size() != n) throw std::invalid_argument("scrub_degraded: units of unequal length");
+            in[i] = units[i]->data();
+        }
+        hec_scrub_result_t r{};
+        check(hec_scrub_degraded(h_.get(), in.data(), n, &r));
+        return make_result(r);
+    }
+    // One presence mask per stripe (hec_scrub_device_mixed): present[s] bit i =
+    // unit i of stripe s is there; d_units[k+m] never null; d_workspace of
+    // scrub_mixed_workspace_size(stripes) bytes, untouched until the stream has
+    // passed the call.  d_results as scrub_device.
+    size_t scrub_mixed_workspace_size(size_t stripes) const {
+        return hec_scrub_mixed_workspace_size(h_.get(), stripes);
+    }
+    void scrub_device_mixed(const std::vector<const uint8_t*>& d_units, const std::vector<size_t>& strides,
+                            const std::vector<uint64_t>& present, size_t cell_len, hec_scrub_result_t* d_results,
+                            void* d_workspace, size_t workspace_bytes, void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_device_mixed: need data_units + parity_units units");
+        check(hec_scrub_device_mixed(h_.get(), d_units.data(), strides.data(), present.data(), cell_len,
+                                     present.size(), d_results, d_workspace, workspace_bytes, hip_stream));
+    }
+
     // Verified reconstruction of a device-resident batch, asynchronous on
     // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
     // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and

@@ -66,6 +66,7 @@ EXPORTS = [
     "hec_reconstruct_mixed_workspace_size", "hec_reconstruct_device_mixed",
     "hec_reconstruct_crc_device", "hec_reconstruct_crc_mixed_workspace_size", "hec_reconstruct_crc_device_mixed",
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
+    "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
 ]
 
 
@@ -191,6 +192,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_verdict": ([ctypes.c_uint64, ctypes.c_uint64, S, ctypes.POINTER(I)], I),
         "hec_scrub": ([P, PP, S, P], I),
         "hec_scrub_device": ([P, PP, SP, S, S, P, P], I),
+        "hec_scrub_plan": ([ctypes.c_char_p, S, S, P, SP, SP, SP, P], I),
+        "hec_scrub_degraded": ([P, PP, S, P], I),
+        "hec_scrub_mixed_workspace_size": ([P, S], S),
+        "hec_scrub_device_mixed": ([P, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, P, P, S, P], I),
     }
     if hasattr(lib, "hec_tune_set"):  # the measurement build only (include/hdfs_ec_amd_exp.h)
         sig["hec_tune_set"] = ([I, I], I)
@@ -335,6 +340,22 @@ def reconstruct_plan(data_units: int, parity_units: int, present: Sequence[bool]
                                     targ, mat))
     t = t.value
     return list(surv) if t else [], list(targ[:t]), [list(mat[r * k:(r + 1) * k]) for r in range(t)]
+
+
+def scrub_plan(data_units: int, parity_units: int, present: Sequence[bool], codec: str = "rs"):
+    """hec_scrub_plan: (survivors, extras, matrix) of the degraded scrub of a
+    stripe with the units of `present`: the first k present units, the other e
+    present units and G = C[extras] . inverse(C[survivors]) as e rows.  e == 0
+    (k units present or fewer: nothing to check against) gives ([], [], [])."""
+    k, m = data_units, parity_units
+    pres = (ctypes.c_uint8 * (k + m))(*[1 if p else 0 for p in present])
+    e = ctypes.c_size_t(0)
+    surv = (ctypes.c_size_t * k)()
+    extras = (ctypes.c_size_t * m)()
+    mat = (ctypes.c_uint8 * (m * k))()
+    _check(lib.hec_scrub_plan(codec.encode(), k, m, pres, ctypes.byref(e), surv, extras, mat))
+    e = e.value
+    return list(surv) if e else [], list(extras[:e]), [list(mat[r * k:(r + 1) * k]) for r in range(e)]
 
 
 def scrub_verdict(ruled_out: int, bad_bytes: int, units: int):
@@ -548,6 +569,38 @@ class Coder:
         memory for `stripes` pairs of uint64 (ruled_out, bad_bytes), zeroed by the call."""
         _check(self._lib.hec_scrub_device(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides), cell_len,
                                           stripes, ctypes.c_void_p(results_ptr), ctypes.c_void_p(stream)))
+
+    def scrub_degraded(self, shards: Sequence[Optional[bytes]]):
+        """hec_scrub_degraded: (ruled_out, bad_bytes) of one stripe, None =
+        missing unit (host routine).  The missing units' bits are set in
+        ruled_out once a position is bad; (0, 0) when k units or fewer are
+        present (nothing to check against)."""
+        import numpy as np
+        n_units = self.data_units + self.parity_units
+        assert len(shards) == n_units
+        ins = [None if d is None else
+               np.ascontiguousarray(np.frombuffer(bytes(d) if not isinstance(d, np.ndarray) else d, dtype=np.uint8))
+               for d in shards]
+        lens = {len(a) for a in ins if a is not None}
+        assert len(lens) <= 1, "equal shard lengths"
+        res = (ctypes.c_uint64 * 2)()
+        _check(self._lib.hec_scrub_degraded(self._h, _pp([0 if a is None else a.ctypes.data for a in ins]),
+                                            lens.pop() if lens else 0, res))
+        return int(res[0]), int(res[1])
+
+    def scrub_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_scrub_mixed_workspace_size(self._h, stripes)
+
+    def scrub_device_mixed(self, shard_ptrs, shard_strides, present_masks, cell_len, stripes, results_ptr,
+                           workspace_ptr, workspace_bytes, stream: int = 0) -> None:
+        """hec_scrub_device_mixed: shard_ptrs[k+m] (none None), one presence
+        mask per stripe; results_ptr as scrub_device, workspace_ptr = device
+        memory of scrub_mixed_workspace_size(stripes) bytes."""
+        masks = None if present_masks is None else (ctypes.c_uint64 * max(stripes, 1))(*present_masks)
+        _check(self._lib.hec_scrub_device_mixed(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides), masks,
+                                                cell_len, stripes, ctypes.c_void_p(results_ptr),
+                                                ctypes.c_void_p(workspace_ptr), workspace_bytes,
+                                                ctypes.c_void_p(stream)))
 
     def prepare_decode(self, missing: Sequence[int], checksum_type: int = 2) -> bool:
         """hec_coder_prepare_decode: compile the plan-specialised fused decode
@@ -895,6 +948,28 @@ def scrub_batch(coder: Coder, cells, stream=None):
     out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
     ptrs, strides = stripe_layout_ptrs(cells, n)
     coder.scrub_device(ptrs, strides, cells.shape[2], S, out.data_ptr(), s.cuda_stream)
+    return out
+
+
+def scrub_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], stream=None, workspace=None):
+    """scrub_batch for degraded stripes: present_masks[s] bit i = unit i of
+    stripe s is there (the other slots of cells are not read).  -> int64 cuda
+    tensor [S, 2]; a stripe with k units or fewer gives (0, 0) unchecked, a bad
+    stripe has its missing units' bits set in ruled_out (scrub_verdict works
+    unchanged).  Pass `workspace` (uint8 cuda tensor of
+    coder.scrub_mixed_workspace_size(S) bytes) to reuse one; it must stay
+    untouched until the stream has passed the call."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    if workspace is None:
+        workspace = torch.empty(max(coder.scrub_mixed_workspace_size(S), 1), dtype=torch.uint8, device=cells.device)
+        workspace.record_stream(s)
+    coder.scrub_device_mixed(ptrs, strides, list(present_masks), cells.shape[2], S, out.data_ptr(),
+                             workspace.data_ptr(), workspace.numel(), s.cuda_stream)
     return out
 
 

@@ -367,8 +367,10 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t *coder, int checksum_type,
  * (`hdfs debug verifyEC`; dfs.datanode.ec.reconstruct.validation, HDFS-15759):
  * are the k+m units of a stripe still consistent, and if not, which one is
  * wrong?  The reference's reader trusts the packet checksums
- * (connection.rs:477-504) and has no counterpart.  All k+m units must be
- * present: scrubbing a stripe with missing units is out of scope.
+ * (connection.rs:477-504) and has no counterpart.  hec_scrub and
+ * hec_scrub_device take stripes whose k+m units are all present; a stripe with
+ * missing units (a dead DataNode) is scrubbed by hec_scrub_degraded and
+ * hec_scrub_device_mixed, defined after them.
  *
  * With C the coder's (k+m) x k matrix (hec_gen_codec_matrix), P = C[k:] and
  * H = [P | I_m] (column t of H is P[:,t] for a data unit t < k and the unit
@@ -435,6 +437,75 @@ int hec_scrub(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len
  * host-only coder. */
 int hec_scrub_device(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
                      size_t cell_len, size_t stripes, hec_scrub_result_t *d_results, void *hip_stream);
+
+/* Degraded scrub: a stripe with missing units.  Of its p present units, S is
+ * the first k in ascending order (the survivors every reconstruction call
+ * picks), E the other e = p - k (the extras, ascending), 0 <= e <= m.  With
+ *   G = C[E] . inverse(select_rows(C, S))            (e x k)
+ * -- the rows hec_reconstruct_plan returns for present = S only, want = E --
+ * the syndrome of byte position b is
+ *   s_j(b) = sum_i G[j][i] * u_{S_i}(b)  ^  u_{E_j}(b),   j < e,
+ * and the parity-check matrix H' has one column per present unit: G[:, i] for
+ * survivor S_i, the unit vector e_j for extra E_j.  With every unit present
+ * S = 0..k-1, E = the parity units and G = P: the scrub above.  Per stripe
+ *   bad_bytes = the number of positions with a non-zero syndrome vector;
+ *   ruled_out = bit t set for a present unit t iff some position's vector is
+ *               not a multiple of t's column of H' (2x2 minors, as above).
+ *   Missing units: when bad_bytes != 0 the bit of every missing unit is set
+ *               too -- a missing unit is never the culprit -- so
+ *               hec_scrub_verdict(ruled_out, bad_bytes, k+m, &unit) works
+ *               unchanged.  A clean stripe gives (0, 0).
+ *   Unchecked stripes: e == 0 (exactly k units present, or fewer) leaves
+ *               nothing to check against.  Such a stripe gives (0, 0), nothing
+ *               of it is read and the call does not fail: one unrecoverable
+ *               group must not fail a scanner's batch.  The caller knows e
+ *               from its own mask (hec_scrub_plan returns it).
+ * With e == 1 nothing can be located (AMBIGUOUS, as m == 1 above); what a
+ * verdict proves is what is said above with e in the place of m.
+ *
+ * hec_scrub_plan (host only): the check plan of a presence mask present[k+m].
+ * *n_checks = e; for e >= 1 survivors[k], extras[e] and matrix[e*k] (G,
+ * row-major) are filled where not NULL; for e == 0 nothing else is written.
+ * Codec names and their errors as hec_reconstruct_plan. */
+int hec_scrub_plan(const char *codec, size_t data_units, size_t parity_units, const uint8_t *present,
+                   size_t *n_checks, size_t *survivors, size_t *extras, uint8_t *matrix);
+
+/* Host drop-in (synchronous): shards[k+m] host buffers of shard_len bytes,
+ * NULL = missing (never read).  Always the host routine of hec_scrub, over
+ * the stripe's [S..., E...] with G; no allocation that grows with shard_len;
+ * works on host-only coders.  With no NULL the result is hec_scrub's.
+ * HEC_ERR_INVALID_ARG for a NULL coder, shards or out, or shard_len == 0. */
+int hec_scrub_degraded(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len,
+                       hec_scrub_result_t *out);
+
+/* Device-resident batch with one presence mask per stripe (asynchronous on
+ * hip_stream), following hec_reconstruct_device_mixed: d_shards[k+m] /
+ * shard_strides[k+m], none NULL (the slots a stripe lacks are not read);
+ * present[stripes] host array, bit i = unit i present.  One plan per distinct
+ * mask is built on the host and cached in the coder; the plans and the launch
+ * counters sit in d_workspace (hec_scrub_mixed_workspace_size(coder, stripes)
+ * bytes of device memory, 16-byte aligned, required whenever a stripe can be
+ * checked), which must stay untouched until the stream reaches the work;
+ * calls in flight at once need different workspaces.  As hec_scrub_device:
+ * d_results[stripes] (8-byte aligned) is zeroed by the call itself on the
+ * stream and then receives each stripe's pair; the pass is read-only over the
+ * present units and clean stripes cost no write.
+ * k in {2,3,6,10}, at most 4 extras in any stripe and 16-B aligned bases,
+ * strides and cell_len run one register kernel with the plans resident in LDS;
+ * a batch whose plans do not fit (RS(10,4) with hundreds of distinct masks)
+ * runs that kernel once per run of consecutive stripes sharing a mask; other
+ * shapes a byte-granular kernel.  The results are the same.
+ * HEC_OK for stripes == 0 (nothing queued) and for a batch with no checkable
+ * stripe (the results are still zeroed).  HEC_ERR_INVALID_ARG, nothing
+ * queued: NULL coder, d_shards, shard_strides, present or d_results, a NULL
+ * d_shards[i], cell_len == 0, misaligned d_results, and -- when a stripe can
+ * be checked -- a NULL, misaligned or too small workspace.  HEC_ERR_DEVICE on
+ * a host-only coder.  Capturing the call into a HIP graph is not supported. */
+size_t hec_scrub_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+int hec_scrub_device_mixed(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
+                           const uint64_t *present, size_t cell_len, size_t stripes,
+                           hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
+                           void *hip_stream);
 
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.

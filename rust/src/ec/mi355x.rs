@@ -116,6 +116,10 @@ unsafe extern "C" {
     fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
     fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
                         stripes: usize, d_results: *mut ScrubResult, stream: *mut c_void) -> c_int;
+    fn hec_scrub_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_scrub_device_mixed(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
+                              present: *const u64, cell_len: usize, stripes: usize, d_results: *mut ScrubResult,
+                              d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
     fn hec_device_alloc(device: c_int, bytes: usize, flags: u32, out: *mut *mut c_void) -> c_int;
     fn hec_device_free(device: c_int, ptr: *mut c_void) -> c_int;
     fn hec_device_copy(device: c_int, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;
@@ -402,6 +406,36 @@ impl GpuCoder {
         assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
         check(unsafe {
             hec_scrub_device(self.raw, shards.as_ptr(), shard_strides.as_ptr(), cell, stripes, results, stream)
+        })
+    }
+
+    /// Device bytes `scrub_device_mixed` needs for `stripes` stripes.
+    pub fn scrub_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_scrub_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// Scrubs a batch of degraded stripes (`hec_scrub_device_mixed`):
+    /// `present[s]` bit i = unit i of stripe s is there; the slots a stripe
+    /// lacks are not read, but no `shards[i]` may be null.  Results as
+    /// `scrub_device`, with the bits of a bad stripe's missing units set in
+    /// `ruled_out`, so `scrub_verdict` works unchanged; a stripe with k units
+    /// or fewer cannot be checked and gives (0, 0).  After a node loss: scrub
+    /// with the masks, clear each `Located(t)` from its mask,
+    /// `reconstruct_device_mixed` in place, scrub again.  `workspace` is device
+    /// memory of `scrub_mixed_workspace_size(stripes)` bytes, untouched until
+    /// `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `scrub_device`; `workspace` valid for `workspace_bytes` on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn scrub_device_mixed(&self, shards: &[*const u8], shard_strides: &[usize], present: &[u64],
+                                     cell: usize, results: *mut ScrubResult, workspace: *mut c_void,
+                                     workspace_bytes: usize, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_device_mixed(self.raw, shards.as_ptr(), shard_strides.as_ptr(), present.as_ptr(), cell,
+                                   present.len(), results, workspace, workspace_bytes, stream)
         })
     }
 
