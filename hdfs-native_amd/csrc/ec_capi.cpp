@@ -20,6 +20,8 @@
 #include <map>
 #include <tuple>
 #include <memory>
+#include <numeric>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -63,7 +65,6 @@ struct DecodePlan {
     std::vector<size_t> survivors;  // k
     std::vector<size_t> missing;    // e
     std::vector<uint8_t> matrix;    // e x k
-    std::vector<uint32_t> perm;     // e x k x 8: the matrix's v_perm product tables (mixed-decode plan blobs)
     std::vector<uint64_t> aff;      // e x k: the matrix's host affine qwords (small-row host path)
     // Reconstruction (hec_reconstruct*): every missing unit, parity included.
     // The fields above stay what the decode calls have always seen; these
@@ -222,10 +223,10 @@ DecodePlan compute_plan(size_t k, size_t m, const uint8_t* present, const std::v
         return p;
     }
     // select_rows(invalid), ascending: `lost` lists the data units first, so
-    // the decode's rows, tables and qwords are the first e of rec_*
+    // the decode's rows and qwords are the first e of rec_* (the mixed decode
+    // reads them there, v_perm tables included)
     const size_t ek = p.missing.size() * k;
     p.matrix.assign(p.rec_matrix.begin(), p.rec_matrix.begin() + ek);
-    p.perm.assign(p.rec_perm.begin(), p.rec_perm.begin() + ek * 8);
     p.aff.assign(p.rec_aff.begin(), p.rec_aff.begin() + ek);
     return p;
 }
@@ -852,37 +853,449 @@ int hec_decode(hec_coder_t* c, const uint8_t* const* shards, size_t shard_len, u
     });
 }
 
-// ---- heterogeneous per-stripe erasure patterns ---------------------------
+// ---- planning shared by the reconstruction, scrub and per-stripe calls -----
+// Everything the four per-stripe ("mixed") device calls do on the host before
+// a kernel is queued, once: which rows of which cached plan a pattern needs
+// (RowPlan), the patterns of a batch (group_stripes), its runs of equal-plan
+// stripes (for_each_run), the worst-case and actual workspace layout
+// (worst_case_plans, workspace_layout, plan_image) and the upload of an image
+// through the coder's two pinned buffers (upload_pinned, upload_plan_image).
+// The uniform reconstruction and scrub calls describe their plans the same way.
+
+}  // extern "C"
 
 namespace {
 
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
-size_t max_plans(size_t k, size_t m, size_t stripes) {
-    // presence masks with >= 1 missing data shard and >= k present: at most
-    // sum_{j=1..m} C(k+m, j)
-    double total = 0, c = 1;
-    for (size_t j = 1; j <= m; j++) {
-        c = c * double(k + m - j + 1) / double(j);
-        total += c;
+// Bits 0 .. n-1.
+inline uint64_t unit_bits(size_t n) { return n >= 64 ? ~uint64_t(0) : (uint64_t(1) << n) - 1; }
+
+// The k of the register kernels (their launchers check the same).
+inline bool register_kernel_k(size_t k) { return k == 2 || k == 3 || k == 6 || k == 10; }
+
+// 16-byte aligned bases and strides of the units in `units`.
+bool aligned16(const uint8_t* const* base, const size_t* stride, uint64_t units) {
+    bool ok = true;
+    for (; units; units &= units - 1) {
+        const int i = __builtin_ctzll(units);
+        ok &= ((reinterpret_cast<uintptr_t>(base[i]) | stride[i]) & 15u) == 0;
+    }
+    return ok;
+}
+
+bool any_null(uint8_t* const* ptrs, uint64_t units) {
+    for (; units; units &= units - 1)
+        if (!ptrs[__builtin_ctzll(units)]) return true;
+    return false;
+}
+
+PlanRef plan_of_mask(hec_coder* c, uint64_t mask) {
+    uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    for (size_t i = 0; i < c->k + c->m; i++) pres[i] = (mask >> i) & 1;
+    return cached_plan(c, pres);
+}
+
+// Rows of a cached plan: what one uniform call, or the stripes of one pattern
+// of a batch, computes.  No row = nothing to do.
+struct RowPlan {
+    PlanRef plan;
+    std::vector<size_t> rows;  // positions in plan->lost
+    uint64_t missing = 0;      // the scrub: units the mask lacks; zero elsewhere
+    size_t unit(size_t r) const { return plan->lost[rows[r]]; }
+    uint64_t units() const {
+        uint64_t u = 0;
+        for (size_t r : rows) u |= uint64_t(1) << plan->lost[r];
+        return u;
+    }
+};
+
+// A RowPlan's coefficient rows and host affine qwords, contiguous: the plan's
+// own arrays where the rows are consecutive, a gathered copy otherwise.
+struct RowCoefs {
+    const uint8_t* matrix = nullptr;
+    const uint64_t* aff = nullptr;
+    std::vector<uint8_t> matrix_store;
+    std::vector<uint64_t> aff_store;
+    RowCoefs(const RowPlan& rp, size_t k) {
+        const DecodePlan& p = *rp.plan;
+        bool consecutive = true;
+        for (size_t r = 0; r < rp.rows.size(); r++) consecutive &= rp.rows[r] == rp.rows[0] + r;
+        if (consecutive) {
+            matrix = p.rec_matrix.data() + rp.rows[0] * k;
+            aff = p.rec_aff.data() + rp.rows[0] * k;
+            return;
+        }
+        for (size_t r : rp.rows) {
+            matrix_store.insert(matrix_store.end(), p.rec_matrix.begin() + r * k, p.rec_matrix.begin() + (r + 1) * k);
+            aff_store.insert(aff_store.end(), p.rec_aff.begin() + r * k, p.rec_aff.begin() + (r + 1) * k);
+        }
+        matrix = matrix_store.data();
+        aff = aff_store.data();
+    }
+};
+
+// A RowPlan's rows over stripes s0 .. s0+count-1 of a device batch: the
+// plan's survivors in, its units out, <= 4 rows per launch.
+int launch_rows(hec_coder* c, const RowPlan& rp, const uint8_t* const* d_shards, const size_t* shard_strides,
+                uint8_t* const* d_out, const size_t* out_strides, size_t cell_len, size_t s0, size_t count,
+                hipStream_t stream) {
+    const size_t k = c->k;
+    const RowCoefs t(rp, k);
+    const uint8_t* in[HEC_MAX_DATA_UNITS];
+    size_t ist[HEC_MAX_DATA_UNITS];
+    uint8_t* out[HEC_MAX_PARITY_UNITS];
+    size_t ost[HEC_MAX_PARITY_UNITS];
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = rp.plan->rec_survivors[r];
+        in[r] = d_shards[u] + s0 * shard_strides[u];
+        ist[r] = shard_strides[u];
+    }
+    for (size_t r = 0; r < rp.rows.size(); r++) {
+        const size_t u = rp.unit(r);
+        out[r] = d_out[u] + s0 * out_strides[u];
+        ost[r] = out_strides[u];
+    }
+    return matmul_batch(c->device, t.matrix, rp.rows.size(), k, in, ist, out, ost, cell_len, count, stream);
+}
+
+// The uniform reconstruction calls, from their arguments to the rows to
+// rebuild: units[k+m] (null = lost) and want[k+m] (NULL = every lost unit).
+// `idle` = the call has no stripe to work on.  HEC_OK with rp->rows empty:
+// nothing to rebuild; otherwise the plan stands and every target has storage.
+int resolve_reconstruct(hec_coder* c, const uint8_t* const* units, const uint8_t* want, uint8_t* const* out,
+                        bool have_out, bool idle, RowPlan* rp) {
+    const size_t n = c->k + c->m;
+    uint64_t mask = 0, want_mask = 0;
+    for (size_t i = 0; i < n; i++)
+        if (units[i]) mask |= uint64_t(1) << i;
+    for (size_t i = 0; want && i < n; i++)
+        if (want[i]) want_mask |= uint64_t(1) << i;
+    if (want_mask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+    rp->plan = plan_of_mask(c, mask);
+    if (!idle) rp->rows = target_rows(*rp->plan, want != nullptr, want_mask);
+    if (rp->rows.empty()) return HEC_OK;
+    if (rp->plan->rec_status != HEC_OK) return rp->plan->rec_status;
+    if (!have_out || any_null(out, rp->units())) return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// The rows a mixed reconstruction needs for one (presence, want) pattern.
+int reconstruct_rows(hec_coder* c, uint64_t mask, uint64_t wmask, RowPlan* rp) {
+    if (!wmask) return HEC_OK;
+    rp->plan = plan_of_mask(c, mask);
+    if (rp->plan->rec_status != HEC_OK) return rp->plan->rec_status;
+    rp->rows = target_rows(*rp->plan, true, wmask);
+    return HEC_OK;
+}
+
+// S = the first k units of `mask`, E = its other units; returns |mask|.
+size_t split_survivors(uint64_t mask, size_t k, uint64_t* smask, uint64_t* emask) {
+    size_t seen = 0;
+    *smask = *emask = 0;
+    for (; mask; mask &= mask - 1, seen++) *(seen < k ? smask : emask) |= mask & -mask;
+    return seen;
+}
+
+// The check plan of a presence mask: the rows of G = C[E] . inverse(C[S]),
+// that is the cached reconstruction plan of `present = S only` with the units
+// of E wanted (rec_survivors = S; lost = every unit outside S).  No row when
+// the mask has no extra (exactly k present, or fewer).
+int scrub_rows(hec_coder* c, uint64_t mask, RowPlan* rp) {
+    uint64_t smask, emask;
+    if (split_survivors(mask, c->k, &smask, &emask) <= c->k) return HEC_OK;
+    rp->plan = plan_of_mask(c, smask);
+    if (rp->plan->rec_status != HEC_OK) return rp->plan->rec_status;
+    rp->rows = target_rows(*rp->plan, true, emask);
+    rp->missing = ~mask & unit_bits(c->k + c->m);
+    return HEC_OK;
+}
+
+// The plan's positions (bit i < k survivor i, bit k + j extra j) as unit indices.
+uint64_t scrub_positions_to_units(const RowPlan& sp, size_t k, uint64_t pos) {
+    uint64_t units = 0;
+    for (size_t i = 0; i < k; i++)
+        if ((pos >> i) & 1) units |= uint64_t(1) << sp.plan->rec_survivors[i];
+    for (size_t j = 0; j < sp.rows.size(); j++)
+        if ((pos >> (k + j)) & 1) units |= uint64_t(1) << sp.unit(j);
+    return units;
+}
+
+// Worst-case distinct plans of a batch: sum over j = j_first .. j_last of
+// C(n, j) * weight(j), j being the units a presence mask lacks, capped by the
+// stripe count.
+template <typename Weight>
+size_t worst_case_plans(size_t n, size_t j_first, size_t j_last, size_t stripes, Weight&& weight) {
+    double total = 0, c = 1;  // C(n, 0)
+    for (size_t j = 0; j <= j_last; j++) {
+        if (j > 0) c = c * double(n - j + 1) / double(j);
+        if (j < j_first) continue;
+        total += c * weight(j);
+        if (total >= double(stripes)) return stripes;
     }
     return std::min(stripes, size_t(total));
 }
 
-size_t plan_bytes(size_t k, size_t m) {
-    return sizeof(hec::DevPlanHeader) + std::min(k, m) * k * sizeof(hec::PermTable);
+// A plan's blob entry: a 64-byte header (hec::DevPlanHeader, or
+// hec::ScrubPlanHeader: the same leading fields), then e x k PermTables
+// (register kernels) or e x k coefficient bytes padded to 16 B (byte kernel).
+static_assert(sizeof(hec::DevPlanHeader) == sizeof(hec::ScrubPlanHeader) &&
+                  offsetof(hec::DevPlanHeader, surv) == offsetof(hec::ScrubPlanHeader, surv) &&
+                  offsetof(hec::DevPlanHeader, miss) == offsetof(hec::ScrubPlanHeader, extras) &&
+                  offsetof(hec::DevPlanHeader, pad) == offsetof(hec::ScrubPlanHeader, missing_lo),
+              "one writer fills both plan headers");
+
+size_t plan_entry_bytes(size_t k, size_t e, bool tables) {
+    return sizeof(hec::ScrubPlanHeader) + (tables ? e * k * sizeof(hec::PermTable) : ((e * k + 15) & ~size_t(15)));
 }
 
-// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters]
-// (hec::MixedArgs)
+void write_plan_entry(uint8_t* at, size_t k, const RowPlan& rp, bool tables) {
+    const DecodePlan& p = *rp.plan;
+    hec::ScrubPlanHeader hdr;
+    std::memset(&hdr, 0, sizeof(hdr));
+    hdr.e = uint32_t(rp.rows.size());
+    for (size_t r = 0; r < k; r++) hdr.surv[r] = uint8_t(p.rec_survivors[r]);
+    for (size_t r = 0; r < rp.rows.size(); r++) hdr.extras[r] = uint8_t(rp.unit(r));
+    hdr.missing_lo = uint32_t(rp.missing);
+    hdr.missing_hi = uint32_t(rp.missing >> 32);
+    std::memcpy(at, &hdr, sizeof(hdr));
+    const size_t row_bytes = tables ? k * sizeof(hec::PermTable) : k;
+    uint8_t* body = at + sizeof(hdr);
+    for (size_t r = 0; r < rp.rows.size(); r++) {
+        const size_t x = rp.rows[r] * k;
+        std::memcpy(body + r * row_bytes,
+                    tables ? static_cast<const void*>(&p.rec_perm[x * 8]) : static_cast<const void*>(&p.rec_matrix[x]),
+                    row_bytes);
+    }
+    const size_t end = sizeof(hdr) + rp.rows.size() * row_bytes;
+    std::memset(at + end, 0, plan_entry_bytes(k, rp.rows.size(), tables) - end);
+}
+
+// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters],
+// blob and counters on kAlign boundaries: the workspace of every mixed call
+// (hec::MixedArgs, hec::ReconArgs, hec::ScrubMixedArgs).
+struct WorkspaceLayout {
+    size_t blob_pos, queue_pos, need;
+};
+
+WorkspaceLayout workspace_layout(size_t stripes, size_t blob_bytes, size_t queue_bytes) {
+    WorkspaceLayout w;
+    w.blob_pos = align_up(stripes * sizeof(uint32_t));
+    w.queue_pos = align_up(w.blob_pos + blob_bytes);
+    w.need = w.queue_pos + queue_bytes;
+    return w;
+}
+
+constexpr size_t kScrubQueueBytes = size_t(hec::kMixedQueues) * hec::kMixedQueueStride;  // one launch
+
+// The four *_workspace_size results: the layout of the worst batch of
+// `stripes` patterns.  Decode: masks with 1 .. m units missing, at most
+// min(k, m) of them data.
 size_t mixed_workspace(size_t k, size_t m, size_t stripes) {
-    const size_t p = max_plans(k, m, stripes);
-    return align_up(align_up(stripes * sizeof(uint32_t)) + p * plan_bytes(k, m)) + hec::kMixedQueueBytes;
+    const size_t p = worst_case_plans(k + m, 1, m, stripes, [](size_t) { return 1.0; });
+    return workspace_layout(stripes, p * plan_entry_bytes(k, std::min(k, m), true), hec::kMixedQueueBytes).need;
 }
 
+// Reconstruction: pairs of (mask, non-empty wanted subset of its j <= m lost
+// units).  Only the fused kernel reads the workspace, and only when offsets +
+// blob fit its resident LDS: the blob term is capped there (a larger batch
+// runs per run of stripes and never touches the workspace).
+size_t recon_workspace(size_t k, size_t m, size_t stripes) {
+    const size_t p = worst_case_plans(k + m, 1, m, stripes, [](size_t j) { return double(uint64_t(1) << j) - 1; });
+    const size_t blob = std::min(p * plan_entry_bytes(k, m, true), size_t(hec::kReconResidentMax));
+    return workspace_layout(stripes, blob, hec::kMixedQueueBytes).need;
+}
+
+// [hec_reconstruct_device_mixed's workspace][stripe lists: u32 x stripes]
+size_t recon_crc_workspace(size_t k, size_t m, size_t stripes) {
+    return align_up(recon_workspace(k, m, stripes)) + align_up(stripes * sizeof(uint32_t));
+}
+
+// Scrub: masks with at least one extra, that is with fewer than m units
+// missing; an entry of either kernel's format.
+size_t scrub_workspace(size_t k, size_t m, size_t stripes) {
+    size_t per = plan_entry_bytes(k, m, false);
+    if (register_kernel_k(k)) per = std::max(per, plan_entry_bytes(k, std::min(m, size_t(hec::kMaxR)), true));
+    const size_t p = worst_case_plans(k + m, 0, m - 1, stripes, [](size_t) { return 1.0; });
+    return workspace_layout(stripes, p * per, kScrubQueueBytes).need;
+}
+
+// `bytes` of host data to d_dst through the coder's two pinned staging images
+// (so the H2D is a real async DMA).  The images alternate; an image is free
+// for reuse once its last upload has run (its event), and c->mixed_mu is held
+// from taking the image until that event is recorded behind the new copy.
+// fill(host) writes every one of the `bytes`.
+template <typename Fill>
+int upload_pinned(hec_coder* c, size_t bytes, void* d_dst, hipStream_t stream, Fill&& fill) {
+    std::lock_guard<std::mutex> lk(c->mixed_mu);
+    const int b = c->mixed_next;
+    c->mixed_next ^= 1;
+    if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
+    else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
+    if (c->mixed_host_bytes[b] < bytes) {
+        if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
+        c->mixed_host[b] = nullptr;
+        c->mixed_host_bytes[b] = 0;
+        const size_t grow = std::max(bytes, 2 * c->mixed_host_bytes[b ^ 1]);
+        HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), grow, hipHostMallocDefault),
+                HEC_ERR_NO_MEMORY);
+        c->mixed_host_bytes[b] = grow;
+    }
+    fill(c->mixed_host[b]);
+    HEC_HIP(hipMemcpyAsync(d_dst, c->mixed_host[b], bytes, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
+    HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
+    return HEC_OK;
+}
+
+// The patterns of a batch and the plan of each.
+constexpr uint32_t kNoPlanId = 0xFFFFFFFFu;
+struct Batch {
+    std::vector<uint32_t> stripe_plan;  // per stripe: its entry of `plans`, or kNoPlanId
+    std::vector<RowPlan> plans;         // in the order the patterns first appear
+    size_t max_e = 0;                   // most rows of one plan
+    uint64_t target_units = 0;          // units some plan computes
+};
+
+struct PatternHash {
+    size_t operator()(const std::pair<uint64_t, uint64_t>& p) const {
+        return size_t((p.first * 0x9E3779B97F4A7C15ull) ^ p.second);
+    }
+};
+
+// One plan per distinct (present[s], want_of(s, mask)) pattern, nothing
+// queued: make(mask, wmask, &rp) fills the pattern's RowPlan (no row = no plan
+// for these stripes) or returns a status, which ends the call.  A batch of
+// `plan_cap` plans or more is HEC_ERR_INVALID_ARG.
+template <typename Want, typename Make>
+int group_stripes(const hec_coder* c, const uint64_t* present, size_t stripes, size_t plan_cap, Want&& want_of,
+                  Make&& make, Batch* b) {
+    const uint64_t all = unit_bits(c->k + c->m);
+    std::unordered_map<std::pair<uint64_t, uint64_t>, uint32_t, PatternHash> ids;
+    b->stripe_plan.resize(stripes);
+    for (size_t s = 0; s < stripes; s++) {
+        const uint64_t mask = present[s] & all;
+        const uint64_t wmask = want_of(s, mask) & all;
+        if (wmask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+        auto it = ids.find({mask, wmask});
+        if (it == ids.end()) {
+            RowPlan rp;
+            const int rc = make(mask, wmask, &rp);
+            if (rc != HEC_OK) return rc;
+            uint32_t id = kNoPlanId;
+            if (!rp.rows.empty()) {
+                if (b->plans.size() >= plan_cap) return HEC_ERR_INVALID_ARG;
+                id = uint32_t(b->plans.size());
+                b->max_e = std::max(b->max_e, rp.rows.size());
+                b->target_units |= rp.units();
+                b->plans.push_back(std::move(rp));
+            }
+            it = ids.emplace(std::make_pair(mask, wmask), id).first;
+        }
+        b->stripe_plan[s] = it->second;
+    }
+    return HEC_OK;
+}
+
+// f(s0, s1, plan id) for each maximal run [s0, s1) of consecutive stripes
+// that share a plan, until one returns non-zero.
+template <typename F>
+int for_each_run(const Batch& b, F&& f) {
+    const size_t stripes = b.stripe_plan.size();
+    for (size_t s0 = 0; s0 < stripes;) {
+        size_t s1 = s0 + 1;
+        while (s1 < stripes && b.stripe_plan[s1] == b.stripe_plan[s0]) s1++;
+        if (b.stripe_plan[s0] != kNoPlanId) {
+            const int rc = f(s0, s1, size_t(b.stripe_plan[s0]));
+            if (rc != 0) return rc;
+        }
+        s0 = s1;
+    }
+    return 0;
+}
+
+// The stripes of every plan, ascending, flat in plan order: plan p's are
+// flat[off[p]] .. flat[off[p + 1] - 1].
+void stripe_lists(const Batch& b, std::vector<uint32_t>* flat, std::vector<size_t>* off) {
+    off->assign(b.plans.size() + 1, 0);
+    for (uint32_t id : b.stripe_plan)
+        if (id != kNoPlanId) (*off)[id + 1]++;
+    for (size_t p = 0; p < b.plans.size(); p++) (*off)[p + 1] += (*off)[p];
+    flat->resize(off->back());
+    std::vector<size_t> at(off->begin(), off->end() - 1);
+    for (size_t s = 0; s < b.stripe_plan.size(); s++)
+        if (b.stripe_plan[s] != kNoPlanId) (*flat)[at[b.stripe_plan[s]]++] = uint32_t(s);
+}
+
+// The workspace image of a batch: the layout, and each plan's offset in the blob.
+struct PlanImage : WorkspaceLayout {
+    size_t blob_bytes = 0;
+    bool tables = true;  // PermTable rows (register kernels), else coefficient bytes
+    std::vector<uint32_t> plan_off;
+};
+
+PlanImage plan_image(const Batch& b, size_t k, bool tables, size_t queue_bytes) {
+    PlanImage img;
+    img.tables = tables;
+    img.plan_off.resize(b.plans.size());
+    for (size_t pi = 0; pi < b.plans.size(); pi++) {
+        img.plan_off[pi] = uint32_t(img.blob_bytes);
+        img.blob_bytes += plan_entry_bytes(k, b.plans[pi].rows.size(), tables);
+    }
+    static_cast<WorkspaceLayout&>(img) = workspace_layout(b.stripe_plan.size(), img.blob_bytes, queue_bytes);
+    return img;
+}
+
+// Writes the image (every byte of img.need: offsets, entries, zeroes in the
+// pads and the counters) and queues its upload to d_workspace.
+int upload_plan_image(hec_coder* c, const Batch& b, const PlanImage& img, void* d_workspace, hipStream_t stream) {
+    return upload_pinned(c, img.need, d_workspace, stream, [&](uint8_t* host) {
+        const size_t stripes = b.stripe_plan.size(), blob_end = img.blob_pos + img.blob_bytes;
+        uint32_t* soff = reinterpret_cast<uint32_t*>(host);
+        for (size_t s = 0; s < stripes; s++)
+            soff[s] = b.stripe_plan[s] == kNoPlanId ? hec::kNoPlan : img.plan_off[b.stripe_plan[s]];
+        std::memset(host + stripes * sizeof(uint32_t), 0, img.blob_pos - stripes * sizeof(uint32_t));
+        for (size_t pi = 0; pi < b.plans.size(); pi++)
+            write_plan_entry(host + img.blob_pos + img.plan_off[pi], c->k, b.plans[pi], img.tables);
+        std::memset(host + blob_end, 0, img.need - blob_end);
+    });
+}
+
+// What hec::MixedArgs, hec::ReconArgs and hec::ScrubMixedArgs share.
+template <typename Args>
+void set_batch_args(Args& a, const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                    const PlanImage& img, uint8_t* ws, size_t cell_len, size_t stripes) {
+    std::memset(&a, 0, sizeof(a));
+    for (size_t i = 0; i < c->k + c->m; i++) {
+        a.base[i] = d_shards[i];
+        a.stride[i] = shard_strides[i];
+    }
+    a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
+    a.plans = ws + img.blob_pos;
+    a.blob_bytes = uint32_t(img.blob_bytes);
+    a.k = int32_t(c->k);
+    a.cell_len = cell_len;
+    a.stripes = stripes;
+}
+
+// One launch per group of <= 4 rows, each with its own counters behind
+// `queues`; returns the first launch result that is not 0.
+template <typename Args, typename Launch>
+int launch_row_groups(Args& a, size_t max_e, uint8_t* queues, Launch&& launch) {
+    for (size_t r0 = 0; r0 < max_e; r0 += hec::kMaxR) {
+        a.row0 = int32_t(r0);
+        a.queue = reinterpret_cast<uint32_t*>(queues + (r0 / hec::kMaxR) * hec::kMixedQueues * hec::kMixedQueueStride);
+        const int rc = launch(a, int(std::min(max_e - r0, size_t(hec::kMaxR))));
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
 
 }  // namespace
+
+extern "C" {
+
+// ---- heterogeneous per-stripe erasure patterns ---------------------------
 
 size_t hec_decode_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
     if (!c) return 0;
@@ -891,171 +1304,59 @@ size_t hec_decode_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
 
 namespace {
 
-// The next of the coder's two pinned staging images (c->mixed_host[*b]) with
-// room for `need` bytes, free for reuse: its last upload has run.  The caller
-// holds c->mixed_mu, fills the image, enqueues the copy and records
-// c->ev_mixed[*b] behind it.
-int pinned_image(hec_coder* c, size_t need, int* b_out) {
-    const int b = c->mixed_next;
-    c->mixed_next ^= 1;
-    *b_out = b;
-    if (!c->ev_mixed[b]) HEC_HIP(hipEventCreateWithFlags(&c->ev_mixed[b], hipEventDisableTiming), HEC_ERR_DEVICE);
-    else HEC_HIP(hipEventSynchronize(c->ev_mixed[b]), HEC_ERR_DEVICE);
-    if (c->mixed_host_bytes[b] < need) {
-        if (c->mixed_host[b]) (void)hipHostFree(c->mixed_host[b]);
-        c->mixed_host[b] = nullptr;
-        c->mixed_host_bytes[b] = 0;
-        const size_t grow = std::max(need, 2 * c->mixed_host_bytes[b ^ 1]);
-        HEC_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->mixed_host[b]), grow, hipHostMallocDefault),
-                HEC_ERR_NO_MEMORY);
-        c->mixed_host_bytes[b] = grow;
-    }
-    return HEC_OK;
-}
-
 // Body of hec_decode_device_mixed.  Shards that no stripe's plan reads may be
 // null here (the verified read's phase 2); the public call requires storage
 // for every shard index.
 int mixed_decode_impl(hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides,
                       uint8_t* const* d_out, const size_t* out_strides, const uint64_t* present, size_t cell_len,
                       size_t stripes, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-    {
-        const size_t k = c->k, m = c->m, n = k + m;
-        const uint64_t all = n >= 64 ? ~uint64_t(0) : ((uint64_t(1) << n) - 1);
-        // 1. plan per distinct mask (host), fail before launching anything
-        std::map<uint64_t, uint16_t> ids;
-        std::vector<PlanRef> plans;
-        std::vector<uint16_t> stripe_plan(stripes);
-        size_t max_e = 0;
-        for (size_t s = 0; s < stripes; s++) {
-            const uint64_t mask = present[s] & all;
-            auto it = ids.find(mask);
-            if (it == ids.end()) {
-                uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-                for (size_t i = 0; i < n; i++) pres[i] = (mask >> i) & 1;
-                const PlanRef p_ref = cached_plan(c, pres);
-                const DecodePlan& p = *p_ref;
-                if (p.status != HEC_OK) return p.status;
-                uint16_t id = 0xFFFF;
-                if (!p.missing.empty()) {
-                    if (plans.size() >= 0xFFFF) return HEC_ERR_INVALID_ARG;
-                    id = uint16_t(plans.size());
-                    plans.push_back(p_ref);
-                    max_e = std::max(max_e, p.missing.size());
-                }
-                it = ids.emplace(mask, id).first;
-            }
-            stripe_plan[s] = it->second;
-        }
-        if (plans.empty()) return HEC_OK;
-        for (const PlanRef& p : plans)
-            for (size_t i : p->missing)
-                if (!d_out[i]) return HEC_ERR_INVALID_ARG;
-        DeviceGuard g(c->device);
-        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const size_t k = c->k, n = c->k + c->m;
+    // 1. plan per distinct mask (host), fail before launching anything: the
+    // missing data units, which lead the plan's `lost`
+    Batch batch;
+    int rc = group_stripes(
+        c, present, stripes, 0xFFFF, [](size_t, uint64_t) { return uint64_t(0); },
+        [&](uint64_t mask, uint64_t, RowPlan* rp) {
+            rp->plan = plan_of_mask(c, mask);
+            if (rp->plan->status != HEC_OK) return rp->plan->status;
+            rp->rows.resize(rp->plan->missing.size());
+            std::iota(rp->rows.begin(), rp->rows.end(), size_t(0));
+            return int(HEC_OK);
+        },
+        &batch);
+    if (rc != HEC_OK) return rc;
+    if (batch.plans.empty()) return HEC_OK;
+    if (any_null(d_out, batch.target_units)) return HEC_ERR_INVALID_ARG;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
 
-        bool aligned = cell_len % 16 == 0;
-        for (size_t i = 0; i < n; i++)
-            aligned &= ((reinterpret_cast<uintptr_t>(d_shards[i]) | shard_strides[i]) & 15u) == 0;
-        for (size_t i = 0; i < k; i++)
-            aligned &= ((reinterpret_cast<uintptr_t>(d_out[i]) | out_strides[i]) & 15u) == 0;
-        const bool fused = aligned && (k == 2 || k == 3 || k == 6 || k == 10);
+    const bool fused = register_kernel_k(k) && cell_len % 16 == 0 &&
+                       aligned16(d_shards, shard_strides, unit_bits(n)) &&
+                       aligned16(d_out, out_strides, unit_bits(k));
+    if (!fused)  // correct for any shape: one uniform-pattern launch per run of stripes sharing a plan
+        return for_each_run(batch, [&](size_t s0, size_t s1, size_t pi) {
+            return launch_rows(c, batch.plans[pi], d_shards, shard_strides, d_out, out_strides, cell_len, s0, s1 - s0,
+                               stream);
+        });
 
-        if (!fused) {
-            // Correct for any shape: one uniform-pattern launch per run of
-            // consecutive stripes sharing a plan.
-            size_t s0 = 0;
-            while (s0 < stripes) {
-                size_t s1 = s0 + 1;
-                while (s1 < stripes && stripe_plan[s1] == stripe_plan[s0]) s1++;
-                if (stripe_plan[s0] != 0xFFFF) {
-                    const DecodePlan& p = *plans[stripe_plan[s0]];
-                    const uint8_t* in[HEC_MAX_DATA_UNITS];
-                    size_t ist[HEC_MAX_DATA_UNITS];
-                    uint8_t* out[HEC_MAX_DATA_UNITS];
-                    size_t ost[HEC_MAX_DATA_UNITS];
-                    for (size_t r = 0; r < k; r++) {
-                        in[r] = d_shards[p.survivors[r]] + s0 * shard_strides[p.survivors[r]];
-                        ist[r] = shard_strides[p.survivors[r]];
-                    }
-                    for (size_t r = 0; r < p.missing.size(); r++) {
-                        out[r] = d_out[p.missing[r]] + s0 * out_strides[p.missing[r]];
-                        ost[r] = out_strides[p.missing[r]];
-                    }
-                    const int rc = matmul_batch(c->device, p.matrix.data(), p.missing.size(), k, in, ist, out, ost,
-                                                cell_len, s1 - s0, stream);
-                    if (rc != HEC_OK) return rc;
-                }
-                s0 = s1;
-            }
-            return HEC_OK;
-        }
+    // 2. workspace image
+    const PlanImage img = plan_image(batch, k, true, hec::kMixedQueueBytes);
+    if (!d_workspace || workspace_bytes < img.need || img.blob_bytes > 0xFFFFFFF0ull) return HEC_ERR_INVALID_ARG;
+    rc = upload_plan_image(c, batch, img, d_workspace, stream);
+    if (rc != HEC_OK) return rc;
 
-        // 2. workspace image: per-stripe plan offsets | plan blobs
-        const size_t blob_pos = align_up(stripes * sizeof(uint32_t));
-        size_t blob_bytes = 0;
-        std::vector<uint32_t> plan_off(plans.size());
-        for (size_t pi = 0; pi < plans.size(); pi++) {
-            plan_off[pi] = uint32_t(blob_bytes);
-            blob_bytes += sizeof(hec::DevPlanHeader) + plans[pi]->missing.size() * k * sizeof(hec::PermTable);
-        }
-        const size_t queue_pos = align_up(blob_pos + blob_bytes);
-        const size_t need = queue_pos + hec::kMixedQueueBytes;
-        if (!d_workspace || workspace_bytes < need || blob_bytes > 0xFFFFFFF0ull) return HEC_ERR_INVALID_ARG;
-        {
-            // one of the coder's two pinned images, free once its last copy has run
-            std::lock_guard<std::mutex> lk(c->mixed_mu);
-            int b;
-            const int irc = pinned_image(c, need, &b);
-            if (irc != HEC_OK) return irc;
-            uint8_t* host = c->mixed_host[b];
-            uint32_t* soff = reinterpret_cast<uint32_t*>(host);
-            for (size_t s_ = 0; s_ < stripes; s_++)
-                soff[s_] = stripe_plan[s_] == 0xFFFF ? hec::kNoPlan : plan_off[stripe_plan[s_]];
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const DecodePlan& p = *plans[pi];
-                auto* hdr = reinterpret_cast<hec::DevPlanHeader*>(host + blob_pos + plan_off[pi]);
-                std::memset(hdr, 0, sizeof(*hdr));
-                hdr->e = uint32_t(p.missing.size());
-                for (size_t r = 0; r < k; r++) hdr->surv[r] = uint8_t(p.survivors[r]);
-                for (size_t r = 0; r < p.missing.size(); r++) hdr->miss[r] = uint8_t(p.missing[r]);
-                std::memcpy(host + blob_pos + plan_off[pi] + sizeof(hec::DevPlanHeader), p.perm.data(),
-                            p.perm.size() * sizeof(uint32_t));
-            }
-            std::memset(host + blob_pos + blob_bytes, 0, need - (blob_pos + blob_bytes));  // pad + zeroed counters
-            HEC_HIP(hipMemcpyAsync(d_workspace, host, need, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
-            HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
-        }
-
-        // 3. one launch per group of <= 4 missing rows
-        hec::MixedArgs a;
-        std::memset(&a, 0, sizeof(a));
-        for (size_t i = 0; i < n; i++) {
-            a.base[i] = d_shards[i];
-            a.stride[i] = shard_strides[i];
-        }
-        for (size_t i = 0; i < k; i++) {
-            a.out[i] = d_out[i];
-            a.out_stride[i] = out_strides[i];
-        }
-        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-        a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
-        a.plans = ws + blob_pos;
-        a.blob_bytes = uint32_t(blob_bytes);
-        a.k = int32_t(k);
-        a.cell_len = cell_len;
-        a.stripes = stripes;
-        for (size_t r0 = 0; r0 < max_e; r0 += hec::kMaxR) {
-            a.row0 = int32_t(r0);
-            a.queue = reinterpret_cast<uint32_t*>(ws + queue_pos + (r0 / hec::kMaxR) * hec::kMixedQueues *
-                                                                          hec::kMixedQueueStride);
-            const int rows = int(std::min(max_e - r0, size_t(hec::kMaxR)));
-            const int rc = hec::launch_decode_mixed(a, rows, c->device, stream);
-            if (rc != 0) return to_status(rc);
-        }
-        return HEC_OK;
+    // 3. one launch per group of <= 4 missing rows
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+    hec::MixedArgs a;
+    set_batch_args(a, c, d_shards, shard_strides, img, ws, cell_len, stripes);
+    for (size_t i = 0; i < k; i++) {
+        a.out[i] = d_out[i];
+        a.out_stride[i] = out_strides[i];
     }
+    return to_status(launch_row_groups(a, batch.max_e, ws + img.queue_pos, [&](const hec::MixedArgs& ar, int rows) {
+        return hec::launch_decode_mixed(ar, rows, c->device, stream);
+    }));
 }
 
 }  // namespace
@@ -1083,98 +1384,20 @@ int hec_decode_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, cons
 // The plan of a presence mask carries a row per lost unit (DecodePlan::rec_*);
 // `want` picks the rows of one call.
 
-namespace {
-
-// One call's targets out of a cached plan: the units, and their rows / host
-// affine qwords gathered contiguously (the plan's own arrays when every lost
-// unit is wanted).
-struct Targets {
-    std::vector<size_t> units;
-    const uint8_t* matrix = nullptr;
-    const uint64_t* aff = nullptr;
-    std::vector<uint8_t> matrix_store;
-    std::vector<uint64_t> aff_store;
-};
-
-void gather_targets(const DecodePlan& p, size_t k, const std::vector<size_t>& rows, Targets& t) {
-    for (size_t r : rows) t.units.push_back(p.lost[r]);
-    if (rows.size() == p.lost.size()) {
-        t.matrix = p.rec_matrix.data();
-        t.aff = p.rec_aff.data();
-        return;
-    }
-    for (size_t r : rows) {
-        t.matrix_store.insert(t.matrix_store.end(), p.rec_matrix.begin() + r * k, p.rec_matrix.begin() + (r + 1) * k);
-        t.aff_store.insert(t.aff_store.end(), p.rec_aff.begin() + r * k, p.rec_aff.begin() + (r + 1) * k);
-    }
-    t.matrix = t.matrix_store.data();
-    t.aff = t.aff_store.data();
-}
-
-// want[k+m] (NULL = every missing unit) as a bit mask; false when a wanted
-// unit is present.
-bool want_bits(const uint8_t* want, const uint8_t* present, size_t n, uint64_t* mask) {
-    *mask = 0;
-    if (!want) return true;
-    for (size_t i = 0; i < n; i++) {
-        if (!want[i]) continue;
-        if (present[i]) return false;
-        *mask |= uint64_t(1) << i;
-    }
-    return true;
-}
-
-// pairs of (presence mask, non-empty wanted subset of its <= m lost units):
-// sum_{j=1..m} C(k+m, j) (2^j - 1), capped by the stripe count
-size_t max_recon_plans(size_t k, size_t m, size_t stripes) {
-    double total = 0, c = 1, pw = 1;
-    for (size_t j = 1; j <= m; j++) {
-        c = c * double(k + m - j + 1) / double(j);
-        pw *= 2;
-        total += c * (pw - 1);
-        if (total >= double(stripes)) return stripes;
-    }
-    return std::min(stripes, size_t(total));
-}
-
-// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters]
-// (hec::ReconArgs; the layout of the mixed decode's workspace).  Only the
-// fused kernel reads it, and only when offsets + blob fit its resident LDS:
-// the blob term is capped there (a larger batch runs per run of stripes and
-// never touches the workspace).
-size_t recon_workspace(size_t k, size_t m, size_t stripes) {
-    const size_t p = max_recon_plans(k, m, stripes);
-    const size_t blob = std::min(p * (sizeof(hec::DevPlanHeader) + m * k * sizeof(hec::PermTable)),
-                                 size_t(hec::kReconResidentMax));
-    return align_up(align_up(stripes * sizeof(uint32_t)) + blob) + hec::kMixedQueueBytes;
-}
-
-}  // namespace
-
 int hec_reconstruct(hec_coder_t* c, const uint8_t* const* shards, size_t shard_len, const uint8_t* want,
                     uint8_t* const* out) {
     if (!c || !shards || shard_len == 0) return HEC_ERR_INVALID_ARG;
     return guarded([&] {
-        const size_t k = c->k, n = c->k + c->m;
-        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-        for (size_t i = 0; i < n; i++) present[i] = shards[i] != nullptr;
-        uint64_t want_mask;
-        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
-        const PlanRef p_ref = cached_plan(c, present);
-        const DecodePlan& p = *p_ref;
-        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
-        if (rows.empty()) return HEC_OK;
-        if (p.rec_status != HEC_OK) return p.rec_status;
-        if (!out) return HEC_ERR_INVALID_ARG;
-        Targets t;
-        gather_targets(p, k, rows, t);
-        for (size_t u : t.units)
-            if (!out[u]) return HEC_ERR_INVALID_ARG;
+        const size_t k = c->k;
+        RowPlan rp;
+        const int rc = resolve_reconstruct(c, shards, want, out, out != nullptr, false, &rp);
+        if (rc != HEC_OK || rp.rows.empty()) return rc;
+        const RowCoefs t(rp, k);
         const uint8_t* in[HEC_MAX_DATA_UNITS];
         uint8_t* dst[HEC_MAX_PARITY_UNITS];
-        for (size_t r = 0; r < k; r++) in[r] = shards[p.rec_survivors[r]];
-        for (size_t r = 0; r < t.units.size(); r++) dst[r] = out[t.units[r]];
-        return code_row(c, t.matrix, t.aff, in, k, dst, t.units.size(), shard_len);
+        for (size_t r = 0; r < k; r++) in[r] = shards[rp.plan->rec_survivors[r]];
+        for (size_t r = 0; r < rp.rows.size(); r++) dst[r] = out[rp.unit(r)];
+        return code_row(c, t.matrix, t.aff, in, k, dst, rp.rows.size(), shard_len);
     });
 }
 
@@ -1184,40 +1407,16 @@ int hec_reconstruct_device(hec_coder_t* c, const uint8_t* const* d_shards, const
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_device");
     if (!c || !d_shards || !shard_strides || cell_len == 0) return HEC_ERR_INVALID_ARG;
     return guarded([&] {
-        const size_t k = c->k, n = c->k + c->m;
-        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-        for (size_t i = 0; i < n; i++) present[i] = d_shards[i] != nullptr;
-        uint64_t want_mask;
-        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
-        const PlanRef p_ref = cached_plan(c, present);
-        const DecodePlan& p = *p_ref;
-        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
-        if (rows.empty()) return HEC_OK;
-        if (p.rec_status != HEC_OK) return p.rec_status;
-        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
-        Targets t;
-        gather_targets(p, k, rows, t);
-        for (size_t u : t.units)
-            if (!d_out[u]) return HEC_ERR_INVALID_ARG;
-        const uint8_t* in[HEC_MAX_DATA_UNITS];
-        size_t ist[HEC_MAX_DATA_UNITS];
-        uint8_t* out[HEC_MAX_PARITY_UNITS];
-        size_t ost[HEC_MAX_PARITY_UNITS];
-        for (size_t r = 0; r < k; r++) {
-            in[r] = d_shards[p.rec_survivors[r]];
-            ist[r] = shard_strides[p.rec_survivors[r]];
-        }
-        for (size_t r = 0; r < t.units.size(); r++) {
-            out[r] = d_out[t.units[r]];
-            ost[r] = out_strides[t.units[r]];
-        }
+        RowPlan rp;
+        const int rc = resolve_reconstruct(c, d_shards, want, d_out, d_out && out_strides, false, &rp);
+        if (rc != HEC_OK || rp.rows.empty()) return rc;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
         // all m parity units of an intact data set: the rows are the coding
         // matrix's parity rows, and launch_gf_matmul (rs_parity_matrix) picks
         // the encode kernels for them -- hec_encode_device by another name
-        return matmul_batch(c->device, t.matrix, t.units.size(), k, in, ist, out, ost, cell_len, stripes,
-                            static_cast<hipStream_t>(hip_stream));
+        return launch_rows(c, rp, d_shards, shard_strides, d_out, out_strides, cell_len, 0, stripes,
+                           static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -1228,52 +1427,19 @@ size_t hec_reconstruct_mixed_workspace_size(const hec_coder_t* c, size_t stripes
 
 namespace {
 
-// One distinct (presence mask, wanted units) pair of a mixed batch.
-struct ReconPlan {
-    PlanRef plan;
-    std::vector<size_t> rows;  // positions in plan->lost
-};
-
 int mixed_reconstruct_impl(hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides,
                            uint8_t* const* d_out, const size_t* out_strides, const uint64_t* present,
                            const uint64_t* want, size_t cell_len, size_t stripes, void* d_workspace,
                            size_t workspace_bytes, void* hip_stream) {
-    const size_t k = c->k, m = c->m, n = k + m;
-    const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
+    const size_t k = c->k, n = c->k + c->m;
     // 1. plan per distinct (present, want) pair (host); fail before launching anything
-    std::map<std::pair<uint64_t, uint64_t>, uint16_t> ids;
-    std::vector<ReconPlan> plans;
-    std::vector<uint16_t> stripe_plan(stripes);
-    size_t max_e = 0;
-    uint64_t target_units = 0;  // units that are a target in some stripe
-    for (size_t s = 0; s < stripes; s++) {
-        const uint64_t mask = present[s] & all;
-        const uint64_t wmask = want ? (want[s] & all) : (all & ~mask);
-        if (wmask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
-        auto it = ids.find({mask, wmask});
-        if (it == ids.end()) {
-            uint16_t id = 0xFFFF;
-            if (wmask) {
-                uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-                for (size_t i = 0; i < n; i++) pres[i] = (mask >> i) & 1;
-                ReconPlan rp;
-                rp.plan = cached_plan(c, pres);
-                if (rp.plan->rec_status != HEC_OK) return rp.plan->rec_status;
-                rp.rows = target_rows(*rp.plan, true, wmask);
-                if (plans.size() >= 0xFFFF) return HEC_ERR_INVALID_ARG;
-                id = uint16_t(plans.size());
-                max_e = std::max(max_e, rp.rows.size());
-                target_units |= wmask;
-                plans.push_back(std::move(rp));
-            }
-            it = ids.emplace(std::make_pair(mask, wmask), id).first;
-        }
-        stripe_plan[s] = it->second;
-    }
-    if (plans.empty()) return HEC_OK;
-    if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
-    for (size_t i = 0; i < n; i++)
-        if (((target_units >> i) & 1) && !d_out[i]) return HEC_ERR_INVALID_ARG;
+    Batch batch;
+    int rc = group_stripes(
+        c, present, stripes, 0xFFFF, [&](size_t s, uint64_t mask) { return want ? want[s] : ~mask; },
+        [&](uint64_t mask, uint64_t wmask, RowPlan* rp) { return reconstruct_rows(c, mask, wmask, rp); }, &batch);
+    if (rc != HEC_OK) return rc;
+    if (batch.plans.empty()) return HEC_OK;
+    if (!d_out || !out_strides || any_null(d_out, batch.target_units)) return HEC_ERR_INVALID_ARG;
     DeviceGuard g(c->device);
     if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -1282,118 +1448,39 @@ int mixed_reconstruct_impl(hec_coder* c, const uint8_t* const* d_shards, const s
     // launch per run of consecutive stripes sharing a plan (as the mixed
     // decode does for the shapes it cannot fuse).
     auto per_run = [&]() -> int {
-        size_t s0 = 0;
-        while (s0 < stripes) {
-            size_t s1 = s0 + 1;
-            while (s1 < stripes && stripe_plan[s1] == stripe_plan[s0]) s1++;
-            if (stripe_plan[s0] != 0xFFFF) {
-                const ReconPlan& rp = plans[stripe_plan[s0]];
-                Targets t;
-                gather_targets(*rp.plan, k, rp.rows, t);
-                const uint8_t* in[HEC_MAX_DATA_UNITS];
-                size_t ist[HEC_MAX_DATA_UNITS];
-                uint8_t* out[HEC_MAX_PARITY_UNITS];
-                size_t ost[HEC_MAX_PARITY_UNITS];
-                for (size_t r = 0; r < k; r++) {
-                    const size_t u = rp.plan->rec_survivors[r];
-                    in[r] = d_shards[u] + s0 * shard_strides[u];
-                    ist[r] = shard_strides[u];
-                }
-                for (size_t r = 0; r < t.units.size(); r++) {
-                    const size_t u = t.units[r];
-                    out[r] = d_out[u] + s0 * out_strides[u];
-                    ost[r] = out_strides[u];
-                }
-                const int rc = matmul_batch(c->device, t.matrix, t.units.size(), k, in, ist, out, ost, cell_len,
-                                            s1 - s0, stream);
-                if (rc != HEC_OK) return rc;
-            }
-            s0 = s1;
-        }
-        return HEC_OK;
+        return for_each_run(batch, [&](size_t s0, size_t s1, size_t pi) {
+            return launch_rows(c, batch.plans[pi], d_shards, shard_strides, d_out, out_strides, cell_len, s0, s1 - s0,
+                               stream);
+        });
     };
 
-    bool aligned = cell_len % 16 == 0 && cell_len <= 0xFFFFFFFFull;  // 32-bit lane offsets into a cell
-    for (size_t i = 0; i < n; i++) {
-        aligned &= ((reinterpret_cast<uintptr_t>(d_shards[i]) | shard_strides[i]) & 15u) == 0;
-        if ((target_units >> i) & 1) aligned &= ((reinterpret_cast<uintptr_t>(d_out[i]) | out_strides[i]) & 15u) == 0;
-    }
-    // 2. workspace image: per-stripe plan offsets | plan blobs | zeroed counters
-    const size_t blob_pos = align_up(stripes * sizeof(uint32_t));
-    size_t blob_bytes = 0;
-    std::vector<uint32_t> plan_off(plans.size());
-    for (size_t pi = 0; pi < plans.size(); pi++) {
-        plan_off[pi] = uint32_t(blob_bytes);
-        blob_bytes += sizeof(hec::DevPlanHeader) + plans[pi].rows.size() * k * sizeof(hec::PermTable);
-    }
-    const bool fused = aligned && (k == 2 || k == 3 || k == 6 || k == 10) &&
-                       hec::reconstruct_mixed_resident(stripes, blob_bytes);
+    // 2. workspace image
+    const PlanImage img = plan_image(batch, k, true, hec::kMixedQueueBytes);
+    const bool fused = register_kernel_k(k) && cell_len % 16 == 0 &&
+                       cell_len <= 0xFFFFFFFFull &&  // 32-bit lane offsets into a cell
+                       aligned16(d_shards, shard_strides, unit_bits(n)) &&
+                       aligned16(d_out, out_strides, batch.target_units) &&
+                       hec::reconstruct_mixed_resident(stripes, img.blob_bytes);
     if (!fused) return per_run();
-
-    const size_t queue_pos = align_up(blob_pos + blob_bytes);
-    const size_t need = queue_pos + hec::kMixedQueueBytes;
-    if (!d_workspace || workspace_bytes < need) return HEC_ERR_INVALID_ARG;
-    {
-        // one of the coder's two pinned images (shared with the mixed decode),
-        // free once its last copy has run
-        std::lock_guard<std::mutex> lk(c->mixed_mu);
-        int b;
-        const int irc = pinned_image(c, need, &b);
-        if (irc != HEC_OK) return irc;
-        uint8_t* host = c->mixed_host[b];
-        uint32_t* soff = reinterpret_cast<uint32_t*>(host);
-        for (size_t s_ = 0; s_ < stripes; s_++)
-            soff[s_] = stripe_plan[s_] == 0xFFFF ? hec::kNoPlan : plan_off[stripe_plan[s_]];
-        std::memset(host + stripes * sizeof(uint32_t), 0, blob_pos - stripes * sizeof(uint32_t));
-        for (size_t pi = 0; pi < plans.size(); pi++) {
-            const DecodePlan& p = *plans[pi].plan;
-            const std::vector<size_t>& rows = plans[pi].rows;
-            uint8_t* at = host + blob_pos + plan_off[pi];
-            auto* hdr = reinterpret_cast<hec::DevPlanHeader*>(at);
-            std::memset(hdr, 0, sizeof(*hdr));
-            hdr->e = uint32_t(rows.size());
-            for (size_t r = 0; r < k; r++) hdr->surv[r] = uint8_t(p.rec_survivors[r]);
-            for (size_t r = 0; r < rows.size(); r++) {
-                hdr->miss[r] = uint8_t(p.lost[rows[r]]);
-                std::memcpy(at + sizeof(hec::DevPlanHeader) + r * k * sizeof(hec::PermTable),
-                            &p.rec_perm[rows[r] * k * 8], k * sizeof(hec::PermTable));
-            }
-        }
-        std::memset(host + blob_pos + blob_bytes, 0, need - (blob_pos + blob_bytes));  // pad + zeroed counters
-        HEC_HIP(hipMemcpyAsync(d_workspace, host, need, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
-        HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
-    }
+    if (!d_workspace || workspace_bytes < img.need) return HEC_ERR_INVALID_ARG;
+    rc = upload_plan_image(c, batch, img, d_workspace, stream);
+    if (rc != HEC_OK) return rc;
 
     // 3. one launch per group of <= 4 target rows
+    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
     hec::ReconArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (size_t i = 0; i < n; i++) {
-        a.base[i] = d_shards[i];
-        a.stride[i] = shard_strides[i];
-        if ((target_units >> i) & 1) {
+    set_batch_args(a, c, d_shards, shard_strides, img, ws, cell_len, stripes);
+    for (size_t i = 0; i < n; i++)
+        if ((batch.target_units >> i) & 1) {
             a.out[i] = d_out[i];
             a.out_stride[i] = out_strides[i];
         }
-    }
-    uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-    a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
-    a.plans = ws + blob_pos;
-    a.blob_bytes = uint32_t(blob_bytes);
-    a.k = int32_t(k);
-    a.cell_len = cell_len;
-    a.stripes = stripes;
-    for (size_t r0 = 0; r0 < max_e; r0 += hec::kMaxR) {
-        a.row0 = int32_t(r0);
-        a.queue = reinterpret_cast<uint32_t*>(ws + queue_pos +
-                                              (r0 / hec::kMaxR) * hec::kMixedQueues * hec::kMixedQueueStride);
-        const int rows = int(std::min(max_e - r0, size_t(hec::kMaxR)));
-        const int rc = hec::launch_reconstruct_mixed(a, rows, c->device, stream);
-        // refused (the runtime would not grant the LDS): every row per run;
-        // rows an earlier launch wrote are written again with the same bytes
-        if (rc == -1) return per_run();
-        if (rc != 0) return to_status(rc);
-    }
-    return HEC_OK;
+    rc = launch_row_groups(a, batch.max_e, ws + img.queue_pos, [&](const hec::ReconArgs& ar, int rows) {
+        return hec::launch_reconstruct_mixed(ar, rows, c->device, stream);
+    });
+    // refused (the runtime would not grant the LDS): every row per run; rows
+    // an earlier launch wrote are written again with the same bytes
+    return rc == -1 ? per_run() : to_status(rc);
 }
 
 }  // namespace
@@ -1477,78 +1564,6 @@ int hec_scrub_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_
 
 // ---- degraded scrub: one presence mask per stripe ---------------------------
 
-namespace {
-
-// The check plan of a presence mask: S = the first k present units, E = the
-// other present units, and the rows of G = C[E] . inverse(C[S]) -- the cached
-// reconstruction plan of `present = S only` with the units of E wanted.
-struct ScrubPlan {
-    PlanRef plan;              // rec_survivors = S; lost = every unit outside S
-    std::vector<size_t> rows;  // positions of E in plan->lost, ascending
-    uint64_t missing = 0;      // units the mask lacks
-};
-
-// False when the mask has no extra (e == 0: exactly k present, or fewer).
-// A plan that could not be built leaves its status in sp->plan->rec_status.
-bool scrub_plan_of(hec_coder* c, uint64_t mask, ScrubPlan* sp) {
-    const size_t k = c->k, n = c->k + c->m;
-    uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS] = {0};
-    uint64_t emask = 0;
-    size_t seen = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (!((mask >> i) & 1)) continue;
-        if (seen < k) pres[i] = 1;
-        else emask |= uint64_t(1) << i;
-        seen++;
-    }
-    if (seen <= k) return false;
-    sp->plan = cached_plan(c, pres);
-    sp->rows = target_rows(*sp->plan, true, emask);
-    sp->missing = ~mask & ((uint64_t(1) << n) - 1);  // n <= 48
-    return true;
-}
-
-// The plan's positions (bit i < k survivor i, bit k + j extra j) as unit indices.
-uint64_t scrub_positions_to_units(const ScrubPlan& sp, size_t k, uint64_t pos) {
-    uint64_t units = 0;
-    for (size_t i = 0; i < k; i++)
-        if ((pos >> i) & 1) units |= uint64_t(1) << sp.plan->rec_survivors[i];
-    for (size_t j = 0; j < sp.rows.size(); j++)
-        if ((pos >> (k + j)) & 1) units |= uint64_t(1) << sp.plan->lost[sp.rows[j]];
-    return units;
-}
-
-// Plans of a batch: every presence mask with at least one extra, that is with
-// fewer than m units missing, capped by the stripe count.
-size_t max_scrub_plans(size_t k, size_t m, size_t stripes) {
-    double total = 0, c = 1;
-    for (size_t j = 0; j < m; j++) {
-        total += c;  // C(k+m, j)
-        if (total >= double(stripes)) return stripes;
-        c = c * double(k + m - j) / double(j + 1);
-    }
-    return std::min(stripes, size_t(total));
-}
-
-// A plan's blob: header + e x k PermTables (register kernel) or coefficient
-// bytes padded to 16 B (byte kernel).
-size_t scrub_plan_bytes(size_t k, size_t e, bool tables) {
-    return sizeof(hec::ScrubPlanHeader) + (tables ? e * k * sizeof(hec::PermTable) : ((e * k + 15) & ~size_t(15)));
-}
-
-bool scrub_fast_k(size_t k) { return k == 2 || k == 3 || k == 6 || k == 10; }
-
-// [per-stripe plan offset: u32 x stripes][plan blob][launch tile counters]
-// (hec::ScrubMixedArgs), sized for the worst batch of `stripes` masks.
-size_t scrub_workspace(size_t k, size_t m, size_t stripes) {
-    size_t per = scrub_plan_bytes(k, m, false);
-    if (scrub_fast_k(k)) per = std::max(per, scrub_plan_bytes(k, std::min(m, size_t(hec::kMaxR)), true));
-    return align_up(align_up(stripes * sizeof(uint32_t)) + max_scrub_plans(k, m, stripes) * per) +
-           size_t(hec::kMixedQueues) * hec::kMixedQueueStride;
-}
-
-}  // namespace
-
 int hec_scrub_plan(const char* codec, size_t data_units, size_t parity_units, const uint8_t* present, size_t* n_checks,
                    size_t* survivors, size_t* extras, uint8_t* matrix) {
     if (!present || !n_checks || data_units == 0 || parity_units == 0 || data_units + parity_units > 64)
@@ -1558,17 +1573,14 @@ int hec_scrub_plan(const char* codec, size_t data_units, size_t parity_units, co
     if (name == "xor" && parity_units != 1) return HEC_ERR_INVALID_ARG;
     const size_t k = data_units, n = data_units + parity_units;
     return guarded([&] {
-        std::vector<uint8_t> pres(n, 0);
-        uint64_t emask = 0;
-        size_t seen = 0;
-        for (size_t i = 0; i < n; i++) {
-            if (!present[i]) continue;
-            if (seen < k) pres[i] = 1;
-            else emask |= uint64_t(1) << i;
-            seen++;
-        }
+        uint64_t mask = 0, smask, emask;
+        for (size_t i = 0; i < n; i++)
+            if (present[i]) mask |= uint64_t(1) << i;
+        const size_t seen = split_survivors(mask, k, &smask, &emask);
         *n_checks = seen > k ? seen - k : 0;
         if (seen <= k) return int(HEC_OK);  // nothing to check against
+        std::vector<uint8_t> pres(n);
+        for (size_t i = 0; i < n; i++) pres[i] = (smask >> i) & 1;
         const std::vector<uint8_t> enc = name == "xor"         ? hec::gen_xor_matrix(data_units)
                                          : name == "rs-legacy" ? hec::gen_rs_legacy_matrix(data_units, parity_units)
                                                                : hec::gen_rs_matrix(data_units, parity_units);
@@ -1592,18 +1604,17 @@ int hec_scrub_degraded(hec_coder_t* c, const uint8_t* const* shards, size_t shar
         uint64_t mask = 0;
         for (size_t i = 0; i < n; i++)
             if (shards[i]) mask |= uint64_t(1) << i;
-        ScrubPlan sp;
-        if (!scrub_plan_of(c, mask, &sp)) return int(HEC_OK);  // e == 0: unchecked, nothing read
-        if (sp.plan->rec_status != HEC_OK) return sp.plan->rec_status;
-        Targets t;
-        gather_targets(*sp.plan, k, sp.rows, t);
+        RowPlan sp;
+        const int rc = scrub_rows(c, mask, &sp);
+        if (rc != HEC_OK || sp.rows.empty()) return rc;  // e == 0: unchecked, nothing read
+        const RowCoefs t(sp, k);
         // the host routine over the permuted unit list [S..., E...] with G in
         // the place of P; its bits are positions of that list
         const uint8_t* units[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
         for (size_t i = 0; i < k; i++) units[i] = shards[sp.plan->rec_survivors[i]];
-        for (size_t j = 0; j < t.units.size(); j++) units[k + j] = shards[t.units[j]];
+        for (size_t j = 0; j < sp.rows.size(); j++) units[k + j] = shards[sp.unit(j)];
         uint64_t pos = 0, bad = 0;
-        hec::host::scrub(hec::host::best_isa(), t.matrix, t.aff, k, t.units.size(), units, shard_len, &pos, &bad);
+        hec::host::scrub(hec::host::best_isa(), t.matrix, t.aff, k, sp.rows.size(), units, shard_len, &pos, &bad);
         out->bad_bytes = bad;
         out->ruled_out = bad ? (scrub_positions_to_units(sp, k, pos) | sp.missing) : 0;
         return int(HEC_OK);
@@ -1628,141 +1639,70 @@ int hec_scrub_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, const
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
     return guarded([&] {
         const size_t k = c->k, n = c->k + c->m;
-        const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
         // 1. plan per distinct mask (host); fail before anything is queued
-        constexpr uint32_t kUnchecked = 0xFFFFFFFFu;
-        std::unordered_map<uint64_t, uint32_t> ids;
-        std::vector<ScrubPlan> plans;
-        std::vector<uint32_t> stripe_plan(stripes);
-        size_t max_e = 0;
+        Batch batch;
         bool pivots = true;  // row 0 of every plan without a zero
-        for (size_t s = 0; s < stripes; s++) {
-            const uint64_t mask = present[s] & all;
-            auto it = ids.find(mask);
-            if (it == ids.end()) {
-                uint32_t id = kUnchecked;
-                ScrubPlan sp;
-                if (scrub_plan_of(c, mask, &sp)) {
-                    if (sp.plan->rec_status != HEC_OK) return sp.plan->rec_status;
-                    id = uint32_t(plans.size());
-                    max_e = std::max(max_e, sp.rows.size());
-                    const uint8_t* row0 = &sp.plan->rec_matrix[sp.rows[0] * k];
-                    for (size_t i = 0; i < k; i++) pivots &= row0[i] != 0;
-                    plans.push_back(std::move(sp));
-                }
-                it = ids.emplace(mask, id).first;
-            }
-            stripe_plan[s] = it->second;
-        }
-        const size_t need = scrub_workspace(k, c->m, stripes);
-        if (!plans.empty() && (!d_workspace || workspace_bytes < need ||
-                               (reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0))
+        int rc = group_stripes(
+            c, present, stripes, kNoPlanId, [](size_t, uint64_t) { return uint64_t(0); },
+            [&](uint64_t mask, uint64_t, RowPlan* sp) {
+                const int src = scrub_rows(c, mask, sp);
+                if (src != HEC_OK || sp->rows.empty()) return src;
+                const uint8_t* row0 = &sp->plan->rec_matrix[sp->rows[0] * k];
+                for (size_t i = 0; i < k; i++) pivots &= row0[i] != 0;
+                return int(HEC_OK);
+            },
+            &batch);
+        if (rc != HEC_OK) return rc;
+        // the worst batch of `stripes` masks, not this one's image
+        if (!batch.plans.empty() && (!d_workspace || workspace_bytes < scrub_workspace(k, c->m, stripes) ||
+                                     (reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0))
             return int(HEC_ERR_INVALID_ARG);
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
         hipStream_t stream = static_cast<hipStream_t>(hip_stream);
         // the kernels only OR and add into the words: zeroed here, in stream order
         HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
-        if (plans.empty()) return int(HEC_OK);  // no stripe can be checked
+        if (batch.plans.empty()) return int(HEC_OK);  // no stripe can be checked
 
         // 2. which kernel: the register kernel's shapes, else the byte kernel
-        bool fast = scrub_fast_k(k) && max_e <= size_t(hec::kMaxR) && pivots && cell_len % 16 == 0 &&
-                    cell_len <= 0xFFFFFFFFull;
-        for (size_t i = 0; fast && i < n; i++)
-            fast = ((reinterpret_cast<uintptr_t>(d_shards[i]) | shard_strides[i]) & 15u) == 0;
+        bool fast = register_kernel_k(k) && batch.max_e <= size_t(hec::kMaxR) && pivots && cell_len % 16 == 0 &&
+                    cell_len <= 0xFFFFFFFFull && aligned16(d_shards, shard_strides, unit_bits(n));
         {
             const uint64_t wave_tile = uint64_t(1024) * (k > 6 ? 2 : 4);  // bytes (ec_scrub_mixed.hip)
             if (fast && ((cell_len + wave_tile - 1) / wave_tile) * stripes > 0xFFF00000ull) fast = false;
         }
 
-        // 3. workspace image: per-stripe plan offsets | plan blobs | zeroed counters
-        const size_t blob_pos = align_up(stripes * sizeof(uint32_t));
-        size_t blob_bytes = 0;
-        std::vector<uint32_t> plan_off(plans.size());
-        for (size_t pi = 0; pi < plans.size(); pi++) {
-            plan_off[pi] = uint32_t(blob_bytes);
-            blob_bytes += scrub_plan_bytes(k, plans[pi].rows.size(), fast);
-        }
-        const size_t queue_pos = align_up(blob_pos + blob_bytes);
-        const size_t image = queue_pos + size_t(hec::kMixedQueues) * hec::kMixedQueueStride;  // <= need
-        {
-            // one of the coder's two pinned images (shared with the mixed
-            // decode and reconstruction), free once its last copy has run
-            std::lock_guard<std::mutex> lk(c->mixed_mu);
-            int b;
-            const int irc = pinned_image(c, image, &b);
-            if (irc != HEC_OK) return irc;
-            uint8_t* host = c->mixed_host[b];
-            uint32_t* soff = reinterpret_cast<uint32_t*>(host);
-            for (size_t s_ = 0; s_ < stripes; s_++)
-                soff[s_] = stripe_plan[s_] == kUnchecked ? hec::kNoPlan : plan_off[stripe_plan[s_]];
-            std::memset(host + stripes * sizeof(uint32_t), 0, image - stripes * sizeof(uint32_t));  // pads, counters
-            for (size_t pi = 0; pi < plans.size(); pi++) {
-                const DecodePlan& p = *plans[pi].plan;
-                const std::vector<size_t>& rows = plans[pi].rows;
-                uint8_t* at = host + blob_pos + plan_off[pi];
-                auto* hdr = reinterpret_cast<hec::ScrubPlanHeader*>(at);
-                hdr->e = uint32_t(rows.size());
-                for (size_t r = 0; r < k; r++) hdr->surv[r] = uint8_t(p.rec_survivors[r]);
-                hdr->missing_lo = uint32_t(plans[pi].missing);
-                hdr->missing_hi = uint32_t(plans[pi].missing >> 32);
-                uint8_t* body = at + sizeof(hec::ScrubPlanHeader);
-                for (size_t r = 0; r < rows.size(); r++) {
-                    hdr->extras[r] = uint8_t(p.lost[rows[r]]);
-                    if (fast)
-                        std::memcpy(body + r * k * sizeof(hec::PermTable), &p.rec_perm[rows[r] * k * 8],
-                                    k * sizeof(hec::PermTable));
-                    else
-                        std::memcpy(body + r * k, &p.rec_matrix[rows[r] * k], k);
-                }
-            }
-            HEC_HIP(hipMemcpyAsync(d_workspace, host, image, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
-            HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
-        }
+        // 3. workspace image, in that kernel's entry format
+        const PlanImage img = plan_image(batch, k, fast, kScrubQueueBytes);
+        rc = upload_plan_image(c, batch, img, d_workspace, stream);
+        if (rc != HEC_OK) return rc;
 
         // 4. launch
-        hec::ScrubMixedArgs a;
-        std::memset(&a, 0, sizeof(a));
-        for (size_t i = 0; i < n; i++) {
-            a.base[i] = d_shards[i];
-            a.stride[i] = shard_strides[i];
-        }
         uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-        a.stripe_off = reinterpret_cast<const uint32_t*>(ws);
-        a.plans = ws + blob_pos;
-        a.blob_bytes = uint32_t(blob_bytes);
-        a.k = int32_t(k);
-        a.cell_len = cell_len;
-        a.stripes = stripes;
+        hec::ScrubMixedArgs a;
+        set_batch_args(a, c, d_shards, shard_strides, img, ws, cell_len, stripes);
         a.results = reinterpret_cast<uint64_t*>(d_results);
-        a.queue = reinterpret_cast<uint32_t*>(ws + queue_pos);
+        a.queue = reinterpret_cast<uint32_t*>(ws + img.queue_pos);
         if (!fast) return to_status(hec::launch_scrub_mixed_bytes(a, c->device, stream));
-        if (hec::scrub_mixed_resident(stripes, blob_bytes)) {
-            const int rc = hec::launch_scrub_mixed(a, int(max_e), c->device, stream);
-            if (rc == 0) return int(HEC_OK);
-            if (rc != -1) return to_status(rc);
+        if (hec::scrub_mixed_resident(stripes, img.blob_bytes)) {
+            const int lrc = hec::launch_scrub_mixed(a, int(batch.max_e), c->device, stream);
+            if (lrc != -1) return to_status(lrc);
             // refused (the runtime would not grant the LDS): per run below
         }
         // Plans past the resident LDS: the same kernel once per run of
         // consecutive stripes sharing a plan, that one plan resident.
-        for (size_t s0 = 0; s0 < stripes;) {
-            size_t s1 = s0 + 1;
-            while (s1 < stripes && stripe_plan[s1] == stripe_plan[s0]) s1++;
-            if (stripe_plan[s0] != kUnchecked) {
-                hec::ScrubMixedArgs r = a;
-                for (size_t i = 0; i < n; i++) r.base[i] = d_shards[i] + s0 * shard_strides[i];
-                r.stripe_off = nullptr;
-                r.plans = ws + blob_pos + plan_off[stripe_plan[s0]];
-                r.blob_bytes = uint32_t(scrub_plan_bytes(k, plans[stripe_plan[s0]].rows.size(), true));
-                r.stripes = s1 - s0;
-                r.results = reinterpret_cast<uint64_t*>(d_results + s0);
-                r.queue = nullptr;
-                const int rc = hec::launch_scrub_mixed(r, int(plans[stripe_plan[s0]].rows.size()), c->device, stream);
-                if (rc != 0) return to_status(rc);
-            }
-            s0 = s1;
-        }
-        return int(HEC_OK);
+        return for_each_run(batch, [&](size_t s0, size_t s1, size_t pi) {
+            const size_t e = batch.plans[pi].rows.size();
+            hec::ScrubMixedArgs r = a;
+            for (size_t i = 0; i < n; i++) r.base[i] = d_shards[i] + s0 * shard_strides[i];
+            r.stripe_off = nullptr;
+            r.plans = ws + img.blob_pos + img.plan_off[pi];
+            r.blob_bytes = uint32_t(plan_entry_bytes(k, e, true));
+            r.stripes = s1 - s0;
+            r.results = reinterpret_cast<uint64_t*>(d_results + s0);
+            r.queue = nullptr;
+            return to_status(hec::launch_scrub_mixed(r, int(e), c->device, stream));
+        });
     });
 }
 
@@ -2568,11 +2508,10 @@ int hec_decode_verify_device(hec_coder_t* c, int checksum_type, const uint8_t* c
 
 namespace {
 
-// One uniform group of stripes of a verified reconstruction: a plan, its
-// target rows, and (mixed form) the device list of the group's stripes.
+// One uniform group of stripes of a verified reconstruction: the rows of a
+// plan, and (mixed form) the device list of the group's stripes.
 struct CrcGroupCall {
-    const DecodePlan* plan;
-    const std::vector<size_t>* rows;
+    const RowPlan* rp;
     size_t stripes;            // stripes of the group (entries of d_list)
     const uint32_t* d_list;    // null: stripes 0 .. stripes-1
 };
@@ -2594,22 +2533,15 @@ int recon_crc_check(const hec_coder* c, int checksum_type, size_t cell_len, size
 // same): k, 512-B chunks, 16-B aligned cells.  The rows per plan and the
 // units' bases are checked per group.
 bool recon_crc_shape(const hec_coder* c, size_t cell_len, size_t bpc) {
-    return (c->k == 2 || c->k == 3 || c->k == 6 || c->k == 10) && bpc == 512 && cell_len % 16 == 0;
+    return register_kernel_k(c->k) && bpc == 512 && cell_len % 16 == 0;
 }
 
 bool recon_crc_group_aligned(const hec_coder* c, const CrcGroupCall& g, const uint8_t* const* d_shards,
                              const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides) {
-    if (g.rows->size() > size_t(hec::kMaxR)) return false;
-    bool ok = true;
-    for (size_t r = 0; r < c->k; r++) {
-        const size_t u = g.plan->rec_survivors[r];
-        ok &= ((reinterpret_cast<uintptr_t>(d_shards[u]) | shard_strides[u]) & 15u) == 0;
-    }
-    for (size_t r : *g.rows) {
-        const size_t u = g.plan->lost[r];
-        ok &= ((reinterpret_cast<uintptr_t>(d_out[u]) | out_strides[u]) & 15u) == 0;
-    }
-    return ok;
+    if (g.rp->rows.size() > size_t(hec::kMaxR)) return false;
+    uint64_t survivors = 0;
+    for (size_t r = 0; r < c->k; r++) survivors |= uint64_t(1) << g.rp->plan->rec_survivors[r];
+    return aligned16(d_shards, shard_strides, survivors) && aligned16(d_out, out_strides, g.rp->units());
 }
 
 // The fused launch of one group.  0 ok, -1 refused by the launcher, else HEC_*.
@@ -2617,7 +2549,7 @@ int recon_crc_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t
                     const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides, size_t cell_len,
                     const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
     const size_t k = c->k, n = c->k + c->m;
-    const DecodePlan& p = *g.plan;
+    const DecodePlan& p = *g.rp->plan;
     hec::MatmulArgs a;
     std::memset(&a, 0, sizeof(a));
     hec::ReconCrcArgs cs;
@@ -2628,15 +2560,15 @@ int recon_crc_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t
         a.in_stride[r] = shard_strides[u];
         cs.shard_id[r] = uint8_t(u);
     }
-    for (size_t j = 0; j < g.rows->size(); j++) {
-        const size_t row = (*g.rows)[j], u = p.lost[row];
+    for (size_t j = 0; j < g.rp->rows.size(); j++) {
+        const size_t row = g.rp->rows[j], u = p.lost[row];
         a.out[j] = d_out[u];
         a.out_stride[j] = out_strides[u];
         cs.shard_id[k + j] = uint8_t(u);
         for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
     }
     a.k = int32_t(k);
-    a.r = int32_t(g.rows->size());
+    a.r = int32_t(g.rp->rows.size());
     a.cell_len = cell_len;
     a.stripes = g.stripes;
     cs.sums = d_sums;
@@ -2663,7 +2595,7 @@ int recon_crc_sums_pass(hec_coder* c, int kind, bool verify, const CrcGroupCall&
     size_t cnt = 0;
     if (verify) {
         for (size_t r = 0; r < k; r++, cnt++) {
-            const size_t u = g.plan->rec_survivors[r];
+            const size_t u = g.rp->plan->rec_survivors[r];
             bases[cnt] = d_shards[u];
             strides[cnt] = shard_strides[u];
             sid[cnt] = uint8_t(u);
@@ -2671,33 +2603,14 @@ int recon_crc_sums_pass(hec_coder* c, int kind, bool verify, const CrcGroupCall&
         return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, nullptr, d_expected,
                                d_bad, stream, g.d_list);
     }
-    for (size_t r : *g.rows) {
-        const size_t u = g.plan->lost[r];
+    for (size_t r = 0; r < g.rp->rows.size(); r++) {
+        const size_t u = g.rp->unit(r);
         bases[cnt] = d_out[u];
         strides[cnt] = out_strides[u];
         sid[cnt++] = uint8_t(u);
     }
     return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, d_sums, nullptr, nullptr,
                            stream, g.d_list);
-}
-
-// [hec_reconstruct_device_mixed's workspace][stripe lists: u32 x stripes]
-size_t recon_crc_workspace(size_t k, size_t m, size_t stripes) {
-    return align_up(recon_workspace(k, m, stripes)) + align_up(stripes * sizeof(uint32_t));
-}
-
-// The stripe lists of a mixed call to the device through one of the coder's
-// two pinned images, as the mixed calls upload their plan offsets.
-int upload_stripe_lists(hec_coder* c, const std::vector<uint32_t>& flat, void* d_dst, hipStream_t stream) {
-    const size_t need = flat.size() * sizeof(uint32_t);
-    std::lock_guard<std::mutex> lk(c->mixed_mu);
-    int b;
-    const int irc = pinned_image(c, need, &b);
-    if (irc != HEC_OK) return irc;
-    std::memcpy(c->mixed_host[b], flat.data(), need);
-    HEC_HIP(hipMemcpyAsync(d_dst, c->mixed_host[b], need, hipMemcpyHostToDevice, stream), HEC_ERR_DEVICE);
-    HEC_HIP(hipEventRecord(c->ev_mixed[b], stream), HEC_ERR_DEVICE);
-    return HEC_OK;
 }
 
 }  // namespace
@@ -2715,23 +2628,13 @@ int hec_reconstruct_crc_device(hec_coder_t* c, int checksum_type, const uint8_t*
                                       hip_stream);
     if (!d_shards || !shard_strides) return HEC_ERR_INVALID_ARG;
     return guarded([&]() -> int {
-        const size_t n = c->k + c->m;
-        uint8_t present[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-        for (size_t i = 0; i < n; i++) present[i] = d_shards[i] != nullptr;
-        uint64_t want_mask;
-        if (!want_bits(want, present, n, &want_mask)) return HEC_ERR_INVALID_ARG;
-        const PlanRef p_ref = cached_plan(c, present);
-        const DecodePlan& p = *p_ref;
-        const std::vector<size_t> rows = target_rows(p, want != nullptr, want_mask);
-        if (rows.empty() || stripes == 0) return HEC_OK;
-        if (p.rec_status != HEC_OK) return p.rec_status;
-        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
-        for (size_t r : rows)
-            if (!d_out[p.lost[r]]) return HEC_ERR_INVALID_ARG;
+        RowPlan rp;
+        const int prc = resolve_reconstruct(c, d_shards, want, d_out, d_out && out_strides, stripes == 0, &rp);
+        if (prc != HEC_OK || rp.rows.empty()) return prc;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
         const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        const CrcGroupCall call{&p, &rows, stripes, nullptr};
+        const CrcGroupCall call{&rp, stripes, nullptr};
         if (recon_crc_shape(c, cell_len, bytes_per_checksum) &&
             recon_crc_group_aligned(c, call, d_shards, shard_strides, d_out, out_strides)) {
             const int rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len,
@@ -2775,63 +2678,36 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
     for (size_t i = 0; i < c->k + c->m; i++)
         if (!d_shards[i]) return HEC_ERR_INVALID_ARG;  // every unit needs storage (present in some stripe)
     return guarded([&]() -> int {
-        const size_t k = c->k, m = c->m, n = k + m;
-        const uint64_t all = (uint64_t(1) << n) - 1;  // n <= 48
         // 1. the distinct (present, want) pairs with a target, each with its
         // plan and the list of its stripes (host); fail before launching anything
-        struct Group {
-            ReconPlan rp;
-            std::vector<uint32_t> list;
-        };
-        std::map<std::pair<uint64_t, uint64_t>, size_t> ids;
-        std::vector<Group> groups;
-        uint64_t target_units = 0;
-        for (size_t s = 0; s < stripes; s++) {
-            const uint64_t mask = present[s] & all;
-            const uint64_t wmask = want ? (want[s] & all) : (all & ~mask);
-            if (wmask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
-            if (!wmask) continue;
-            auto it = ids.find({mask, wmask});
-            if (it == ids.end()) {
-                uint8_t pres[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-                for (size_t i = 0; i < n; i++) pres[i] = (mask >> i) & 1;
-                Group g;
-                g.rp.plan = cached_plan(c, pres);
-                if (g.rp.plan->rec_status != HEC_OK) return g.rp.plan->rec_status;
-                g.rp.rows = target_rows(*g.rp.plan, true, wmask);
-                target_units |= wmask;
-                it = ids.emplace(std::make_pair(mask, wmask), groups.size()).first;
-                groups.push_back(std::move(g));
-            }
-            groups[it->second].list.push_back(uint32_t(s));
-        }
-        if (groups.empty()) return HEC_OK;
-        if (!d_out || !out_strides) return HEC_ERR_INVALID_ARG;
-        for (size_t i = 0; i < n; i++)
-            if (((target_units >> i) & 1) && !d_out[i]) return HEC_ERR_INVALID_ARG;
+        Batch batch;
+        int rc = group_stripes(
+            c, present, stripes, kNoPlanId, [&](size_t s, uint64_t mask) { return want ? want[s] : ~mask; },
+            [&](uint64_t mask, uint64_t wmask, RowPlan* rp) { return reconstruct_rows(c, mask, wmask, rp); }, &batch);
+        if (rc != HEC_OK) return rc;
+        if (batch.plans.empty()) return HEC_OK;
+        if (!d_out || !out_strides || any_null(d_out, batch.target_units)) return HEC_ERR_INVALID_ARG;
         // 2. the lists, flat, behind the plain mixed call's part of the workspace
-        const size_t lists_pos = align_up(recon_workspace(k, m, stripes));
+        const size_t lists_pos = align_up(recon_workspace(c->k, c->m, stripes));
         std::vector<uint32_t> flat;
-        std::vector<size_t> off(groups.size());
-        for (size_t gi = 0; gi < groups.size(); gi++) {
-            off[gi] = flat.size();
-            flat.insert(flat.end(), groups[gi].list.begin(), groups[gi].list.end());
-        }
-        if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) ||
-            workspace_bytes < lists_pos + flat.size() * sizeof(uint32_t))
+        std::vector<size_t> off;
+        stripe_lists(batch, &flat, &off);
+        const size_t lists_bytes = flat.size() * sizeof(uint32_t);
+        if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) || workspace_bytes < lists_pos + lists_bytes)
             return HEC_ERR_INVALID_ARG;
-        const uint32_t* d_lists = reinterpret_cast<const uint32_t*>(static_cast<uint8_t*>(d_workspace) + lists_pos);
-        std::vector<CrcGroupCall> calls(groups.size());
+        uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
+        std::vector<CrcGroupCall> calls(batch.plans.size());
         bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum);
-        for (size_t gi = 0; gi < groups.size(); gi++) {
-            calls[gi] = CrcGroupCall{groups[gi].rp.plan.get(), &groups[gi].rp.rows, groups[gi].list.size(),
-                                     d_lists + off[gi]};
+        for (size_t gi = 0; gi < calls.size(); gi++) {
+            calls[gi] = CrcGroupCall{&batch.plans[gi], off[gi + 1] - off[gi],
+                                     reinterpret_cast<const uint32_t*>(d_lists) + off[gi]};
             fused = fused && recon_crc_group_aligned(c, calls[gi], d_shards, shard_strides, d_out, out_strides);
         }
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
         const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        int rc = upload_stripe_lists(c, flat, static_cast<uint8_t*>(d_workspace) + lists_pos, stream);
+        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+                           [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
         if (rc != HEC_OK) return rc;
         // 3. one launch per pair ...
         if (fused) {

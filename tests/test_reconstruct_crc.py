@@ -2,8 +2,11 @@
 no GPU: the symbols, the header, and the argument checks that return before
 anything touches a device."""
 import ctypes
+import json
 import os
 import re
+
+import pytest
 
 import hdfs_native_ec as H
 from conftest import ROOT
@@ -49,6 +52,32 @@ def test_null_coder_is_invalid():
     assert _null_call(None, False) == H.HEC_ERR_INVALID_ARG
     assert _null_call(None, True) == H.HEC_ERR_INVALID_ARG
     assert H.lib.hec_reconstruct_crc_mixed_workspace_size(None, 16) == 0
+
+
+def _recorded_workspace_sizes():
+    with open(os.path.join(ROOT, "tests", "golden", "mixed_workspace_sizes.json")) as f:
+        table = json.load(f)
+    return [(key, stripes, dict(zip(table["calls"], row)))
+            for key, rows in table["sizes"].items() for stripes, row in zip(table["stripes"], rows)]
+
+
+@pytest.mark.parametrize("key,stripes,recorded", _recorded_workspace_sizes(),
+                         ids=[f"{key}-{stripes}" for key, stripes, _ in _recorded_workspace_sizes()])
+def test_mixed_workspace_sizes_are_exact(key, stripes, recorded):
+    """The four *_workspace_size calls against the values recorded from the
+    library as it stood before the mixed calls shared one host-side planner
+    (tests/golden/mixed_workspace_sizes.json; never regenerated from the code
+    under test): a caller's allocation does not change by a byte."""
+    codec, k, m = key.split("-")
+    c = H.Coder(int(k), int(m), H.HEC_DEVICE_HOST, codec=codec)
+    try:
+        got = {"decode": c.decode_mixed_workspace_size(stripes),
+               "reconstruct": c.reconstruct_mixed_workspace_size(stripes),
+               "scrub": c.scrub_mixed_workspace_size(stripes),
+               "reconstruct_crc": c.reconstruct_crc_mixed_workspace_size(stripes)}
+    finally:
+        c.close()
+    assert got == recorded
 
 
 def test_workspace_size_grows_with_stripes():
