@@ -37,6 +37,7 @@
 #include "checksum_tables.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
+#include "ec_scrub_crc.hpp"
 #include "gf256.hpp"
 #include "host_gf.hpp"
 #include "jit.hpp"
@@ -2734,6 +2735,268 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
+    });
+}
+
+// ---- verified scrub: parity check and chunk checksums in one pass -------------
+// hec_scrub_crc_device*: the scrub calls with the chunk sums of every present
+// unit verified in the same pass (ec_scrub_crc.hip), or as a composition of
+// internal launches where the fused kernel does not take the shape.
+
+}  // extern "C"
+
+namespace {
+
+// [hec_scrub_device_mixed's workspace][stripe lists: u32 x stripes]
+size_t scrub_crc_workspace(size_t k, size_t m, size_t stripes) {
+    return align_up(scrub_workspace(k, m, stripes)) + align_up(stripes * sizeof(uint32_t));
+}
+
+// What both entry points check the same way; kind < 0 = HEC_CHECKSUM_NULL.
+int scrub_crc_check(const hec_coder* c, int checksum_type, const uint8_t* const* d_shards, const size_t* shard_strides,
+                    size_t cell_len, size_t stripes, size_t bpc, const uint8_t* d_expected, const uint8_t* d_bad,
+                    const hec_scrub_result_t* d_results, int* kind) {
+    if (!c || !d_shards || !shard_strides || cell_len == 0 || bpc == 0 || !d_results ||
+        (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0 || stripes > SIZE_MAX / sizeof(hec_scrub_result_t))
+        return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;
+    *kind = -1;
+    if (checksum_type == HEC_CHECKSUM_NULL) return HEC_OK;
+    *kind = crc_kind(checksum_type);
+    if (*kind < 0 || !d_expected || !d_bad || (reinterpret_cast<uintptr_t>(d_expected) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// The shapes gf_scrub_crc takes (launch_scrub_crc checks the same): k, 512-B
+// chunks, 16-B aligned cells, tile indices in 32 bits (counted in its smaller
+// block tile, 16 KiB).  The extras and row 0 of every plan are checked per plan.
+bool scrub_crc_shape(const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
+                     size_t stripes, size_t bpc) {
+    if (!register_kernel_k(c->k) || bpc != 512 || cell_len % 16 != 0 || cell_len / 16 > 0xFFFFFFFFull ||
+        stripes > 0xFFFFFFFFull)
+        return false;
+    const uint64_t tiles = (uint64_t(cell_len) + 16383) / 16384;
+    if (tiles > 0xFFFFFFFFull / stripes) return false;
+    return aligned16(d_shards, shard_strides, unit_bits(c->k + c->m));
+}
+
+// At most kMaxR extras and no zero in row 0 of G (the minors divide by it).
+bool scrub_crc_plan_fits(const hec_coder* c, const RowPlan& sp) {
+    if (sp.rows.empty() || sp.rows.size() > size_t(hec::kMaxR)) return false;
+    const uint8_t* row0 = &sp.plan->rec_matrix[sp.rows[0] * c->k];
+    bool pivots = true;
+    for (size_t i = 0; i < c->k; i++) pivots &= row0[i] != 0;
+    return pivots;
+}
+
+// One group of stripes that share a presence mask: its check plan (null: e ==
+// 0, sums only) and (mixed form) the device list of its stripes.
+struct ScrubCrcGroup {
+    uint64_t mask;
+    const RowPlan* sp;
+    size_t stripes;          // stripes of the group (entries of d_list)
+    const uint32_t* d_list;  // null: stripes 0 .. stripes-1
+};
+
+// The fused launch of one group.  0 ok, -1 refused by the launcher, else HEC_*.
+int scrub_crc_fused(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_t* const* d_shards,
+                    const size_t* shard_strides, size_t cell_len, const uint8_t* d_expected, uint8_t* d_bad,
+                    hec_scrub_result_t* d_results, hipStream_t stream) {
+    const size_t k = c->k, n = c->k + c->m;
+    const DecodePlan& p = *g.sp->plan;
+    hec::MatmulArgs a;
+    std::memset(&a, 0, sizeof(a));
+    hec::ScrubCrcArgs cs;
+    std::memset(&cs, 0, sizeof(cs));
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = p.rec_survivors[r];
+        a.in[r] = d_shards[u];
+        a.in_stride[r] = shard_strides[u];
+        cs.shard_id[r] = uint8_t(u);
+    }
+    for (size_t j = 0; j < g.sp->rows.size(); j++) {
+        const size_t row = g.sp->rows[j], u = p.lost[row];
+        a.in[k + j] = d_shards[u];
+        a.in_stride[k + j] = shard_strides[u];
+        cs.shard_id[k + j] = uint8_t(u);
+        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+    }
+    a.k = int32_t(k);
+    a.r = int32_t(g.sp->rows.size());
+    a.cell_len = cell_len;
+    a.stripes = g.stripes;
+    cs.expected = d_expected;
+    cs.bad = d_bad;
+    cs.results = reinterpret_cast<uint64_t*>(d_results);
+    cs.missing = g.sp->missing;
+    cs.n_total = uint32_t(n);
+    cs.kind = kind;
+    cs.stripe_list = g.d_list;
+    const int rc = hec::launch_scrub_crc(a, cs, c->device, stream);
+    if (rc <= 0) return rc;
+    return to_status(rc);
+}
+
+// The present units of a group verified against their sums: the composition's
+// first step, and all there is to do for a group with e == 0.
+int scrub_crc_verify(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_t* const* d_shards,
+                     const size_t* shard_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                     uint8_t* d_bad, hipStream_t stream) {
+    const size_t n = c->k + c->m;
+    const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t strides[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    uint8_t sid[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t cnt = 0;
+    for (size_t u = 0; u < n; u++) {
+        if (!((g.mask >> u) & 1)) continue;
+        bases[cnt] = d_shards[u];
+        strides[cnt] = shard_strides[u];
+        sid[cnt++] = uint8_t(u);
+    }
+    if (cnt == 0) return HEC_OK;
+    return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, nullptr, d_expected, d_bad,
+                           stream, g.d_list);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_scrub_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                         const size_t* shard_strides, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                         const uint8_t* d_expected, uint8_t* d_bad, hec_scrub_result_t* d_results, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_device");
+    int kind;
+    const int chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
+                                    d_expected, d_bad, d_results, &kind);
+    if (chk != HEC_OK) return chk;
+    if (stripes == 0) return HEC_OK;
+    if (kind < 0) return hec_scrub_device(c, d_shards, shard_strides, cell_len, stripes, d_results, hip_stream);
+    return guarded([&]() -> int {
+        // every unit present: S = the data units, E = the parity units, G = P
+        const uint64_t all = unit_bits(c->k + c->m);
+        RowPlan sp;
+        const int prc = scrub_rows(c, all, &sp);
+        if (prc != HEC_OK) return prc;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const ScrubCrcGroup call{all, &sp, stripes, nullptr};
+        if (scrub_crc_plan_fits(c, sp) &&
+            scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum)) {
+            // the kernel only ORs and adds into the words: zeroed here, in
+            // stream order (a zeroing kernel node under capture)
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            const int rc = scrub_crc_fused(c, kind, call, d_shards, shard_strides, cell_len, d_expected, d_bad,
+                                           d_results, stream);
+            if (rc != -1) return rc;  // -1: refused, no kernel launched
+        }
+        // the composition: verify every unit, then the plain scrub (which zeroes the results)
+        const int rc = scrub_crc_verify(c, kind, call, d_shards, shard_strides, cell_len, bytes_per_checksum,
+                                        d_expected, d_bad, stream);
+        if (rc != HEC_OK) return rc;
+        return hec_scrub_device(c, d_shards, shard_strides, cell_len, stripes, d_results, hip_stream);
+    });
+}
+
+size_t hec_scrub_crc_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return scrub_crc_workspace(c->k, c->m, stripes);
+}
+
+int hec_scrub_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                               const size_t* shard_strides, const uint64_t* present, size_t cell_len, size_t stripes,
+                               size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                               hec_scrub_result_t* d_results, void* d_workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_device_mixed");
+    int kind;
+    const int chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
+                                    d_expected, d_bad, d_results, &kind);
+    if (chk != HEC_OK || !present) return chk != HEC_OK ? chk : HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    if (kind < 0)
+        return hec_scrub_device_mixed(c, d_shards, shard_strides, present, cell_len, stripes, d_results, d_workspace,
+                                      workspace_bytes, hip_stream);
+    return guarded([&]() -> int {
+        const size_t k = c->k, m = c->m;
+        const uint64_t all = unit_bits(k + m);
+        // 1. plan per distinct mask with an extra (host), and the masks
+        // without one that still have a unit to verify; fail before anything
+        // is queued
+        Batch batch;
+        bool fits = true;  // every plan within the fused kernel's rows and pivots
+        int rc = group_stripes(
+            c, present, stripes, kNoPlanId, [](size_t, uint64_t) { return uint64_t(0); },
+            [&](uint64_t mask, uint64_t, RowPlan* sp) {
+                const int src = scrub_rows(c, mask, sp);
+                if (src != HEC_OK || sp->rows.empty()) return src;
+                fits = fits && scrub_crc_plan_fits(c, *sp);
+                return int(HEC_OK);
+            },
+            &batch);
+        if (rc != HEC_OK) return rc;
+        std::map<uint64_t, std::vector<uint32_t>> bare;  // e == 0: mask -> its stripes, ascending
+        for (size_t s = 0; s < stripes; s++)
+            if (batch.stripe_plan[s] == kNoPlanId && (present[s] & all)) bare[present[s] & all].push_back(uint32_t(s));
+        const bool idle = batch.plans.empty() && bare.empty();  // no stripe has a unit
+        const size_t lists_pos = align_up(scrub_workspace(k, m, stripes));
+        if (!idle && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0 ||
+                      workspace_bytes < scrub_crc_workspace(k, m, stripes)))
+            return HEC_ERR_INVALID_ARG;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const bool fused = fits && scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        if (idle || fused)  // the composition's scrub call zeroes them itself
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        if (idle) return HEC_OK;
+        // 2. the lists, flat -- the plans' and then the bare masks' -- behind
+        // the plain mixed call's part of the workspace
+        std::vector<uint32_t> flat;
+        std::vector<size_t> off;
+        stripe_lists(batch, &flat, &off);
+        for (const auto& b : bare) {
+            flat.insert(flat.end(), b.second.begin(), b.second.end());
+            off.push_back(flat.size());
+        }
+        const size_t lists_bytes = flat.size() * sizeof(uint32_t);
+        uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
+        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+                           [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
+        if (rc != HEC_OK) return rc;
+        std::vector<ScrubCrcGroup> groups;
+        for (size_t gi = 0; gi < batch.plans.size(); gi++)
+            groups.push_back(ScrubCrcGroup{all & ~batch.plans[gi].missing, &batch.plans[gi], off[gi + 1] - off[gi],
+                                           reinterpret_cast<const uint32_t*>(d_lists) + off[gi]});
+        size_t gi = batch.plans.size();
+        for (const auto& b : bare) {
+            groups.push_back(ScrubCrcGroup{b.first, nullptr, off[gi + 1] - off[gi],
+                                           reinterpret_cast<const uint32_t*>(d_lists) + off[gi]});
+            gi++;
+        }
+        // 3. one launch per mask: the fused kernel, or sums only where e == 0 ...
+        if (fused) {
+            for (const ScrubCrcGroup& grp : groups) {
+                rc = grp.sp ? scrub_crc_fused(c, kind, grp, d_shards, shard_strides, cell_len, d_expected, d_bad,
+                                              d_results, stream)
+                            : scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum,
+                                               d_expected, d_bad, stream);
+                if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
+            }
+            return HEC_OK;
+        }
+        // ... or the composition: verify per mask, then the plain mixed scrub
+        for (const ScrubCrcGroup& grp : groups) {
+            rc = scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
+                                  d_bad, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return hec_scrub_device_mixed(c, d_shards, shard_strides, present, cell_len, stripes, d_results, d_workspace,
+                                      lists_pos, hip_stream);
     });
 }
 

@@ -230,6 +230,39 @@ class Coder {
                                      present.size(), d_results, d_workspace, workspace_bytes, hip_stream));
     }
 
+    // Verified scrub (hec_scrub_crc_device): scrub_device with every unit's
+    // chunk sums verified in the same pass against d_expected
+    // ([stripe][k+m][nck] big-endian u32); a mismatch sets
+    // d_bad[stripe * (k+m) + unit] (zeroed by the caller).  d_results as
+    // scrub_device; the two outputs are independent.
+    void scrub_crc_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                          const std::vector<size_t>& strides, size_t cell_len, size_t stripes,
+                          size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                          hec_scrub_result_t* d_results, void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_crc_device: need data_units + parity_units units");
+        check(hec_scrub_crc_device(h_.get(), checksum_type, d_units.data(), strides.data(), cell_len, stripes,
+                                   bytes_per_checksum, d_expected, d_bad, d_results, hip_stream));
+    }
+    // One presence mask per stripe (hec_scrub_crc_device_mixed): only present
+    // units are read and verified, also where k units or fewer are present;
+    // d_workspace of scrub_crc_mixed_workspace_size(stripes) bytes, untouched
+    // until the stream has passed the call.
+    size_t scrub_crc_mixed_workspace_size(size_t stripes) const {
+        return hec_scrub_crc_mixed_workspace_size(h_.get(), stripes);
+    }
+    void scrub_crc_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                const std::vector<size_t>& strides, const std::vector<uint64_t>& present,
+                                size_t cell_len, size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                hec_scrub_result_t* d_results, void* d_workspace, size_t workspace_bytes,
+                                void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_crc_device_mixed: need data_units + parity_units units");
+        check(hec_scrub_crc_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(), present.data(),
+                                         cell_len, present.size(), bytes_per_checksum, d_expected, d_bad, d_results,
+                                         d_workspace, workspace_bytes, hip_stream));
+    }
+
     // Verified reconstruction of a device-resident batch, asynchronous on
     // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
     // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and

@@ -67,6 +67,7 @@ EXPORTS = [
     "hec_reconstruct_crc_device", "hec_reconstruct_crc_mixed_workspace_size", "hec_reconstruct_crc_device_mixed",
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
+    "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
 ]
 
 
@@ -196,6 +197,9 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_degraded": ([P, PP, S, P], I),
         "hec_scrub_mixed_workspace_size": ([P, S], S),
         "hec_scrub_device_mixed": ([P, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, P, P, S, P], I),
+        "hec_scrub_crc_device": ([P, I, PP, SP, S, S, S, P, P, P, P], I),
+        "hec_scrub_crc_mixed_workspace_size": ([P, S], S),
+        "hec_scrub_crc_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
     }
     if hasattr(lib, "hec_tune_set"):  # the measurement build only (include/hdfs_ec_amd_exp.h)
         sig["hec_tune_set"] = ([I, I], I)
@@ -602,6 +606,34 @@ class Coder:
                                                 ctypes.c_void_p(workspace_ptr), workspace_bytes,
                                                 ctypes.c_void_p(stream)))
 
+    def scrub_crc_device(self, shard_ptrs, shard_strides, cell_len, stripes, expected_ptr, bad_ptr, results_ptr,
+                         bytes_per_checksum: int = 512, checksum_type: int = CHECKSUM_CRC32C,
+                         stream: int = 0) -> None:
+        """hec_scrub_crc_device: scrub_device with every unit's chunk sums
+        verified in the same pass against expected_ptr ([stripe][k+m][nck]
+        big-endian u32); a mismatch sets bad_ptr[stripe * (k+m) + unit] (flags
+        zeroed by the caller).  results_ptr as scrub_device."""
+        _check(self._lib.hec_scrub_crc_device(self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]),
+                                              _sp(shard_strides), cell_len, stripes, bytes_per_checksum,
+                                              ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+                                              ctypes.c_void_p(results_ptr), ctypes.c_void_p(stream)))
+
+    def scrub_crc_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_scrub_crc_mixed_workspace_size(self._h, stripes)
+
+    def scrub_crc_device_mixed(self, shard_ptrs, shard_strides, present_masks, cell_len, stripes, expected_ptr,
+                               bad_ptr, results_ptr, workspace_ptr, workspace_bytes, bytes_per_checksum: int = 512,
+                               checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_scrub_crc_device_mixed: scrub_device_mixed with the checksum
+        buffers of scrub_crc_device (only the present units are verified); the
+        workspace is scrub_crc_mixed_workspace_size(stripes) bytes."""
+        masks = None if present_masks is None else (ctypes.c_uint64 * max(stripes, 1))(*present_masks)
+        _check(self._lib.hec_scrub_crc_device_mixed(self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]),
+                                                    _sp(shard_strides), masks, cell_len, stripes, bytes_per_checksum,
+                                                    ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+                                                    ctypes.c_void_p(results_ptr), ctypes.c_void_p(workspace_ptr),
+                                                    workspace_bytes, ctypes.c_void_p(stream)))
+
     def prepare_decode(self, missing: Sequence[int], checksum_type: int = 2) -> bool:
         """hec_coder_prepare_decode: compile the plan-specialised fused decode
         + verify kernel for shards `missing` unavailable, now; True when it
@@ -971,6 +1003,56 @@ def scrub_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], stream=
     coder.scrub_device_mixed(ptrs, strides, list(present_masks), cells.shape[2], S, out.data_ptr(),
                              workspace.data_ptr(), workspace.numel(), s.cuda_stream)
     return out
+
+
+def scrub_crc_batch(coder: Coder, cells, expected, bad=None, checksum_type: int = CHECKSUM_CRC32C, stream=None):
+    """scrub_batch with the chunk checksums in the same pass: expected is a
+    cuda tensor of S * (k+m) * ceil(cell / 512) 4-byte words (int32 or 4 uint8
+    each; big-endian sums) that every unit is verified against.  -> (results,
+    bad): the int64 [S, 2] tensor of scrub_batch and the uint8 [S, k+m] flags
+    (1 = the unit does not match its sums).  Pass `bad` to accumulate into a
+    tensor of your own (flags are only ever set); otherwise a zeroed one is
+    made.  Read-only over cells and expected; asynchronous on the stream."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    with torch.cuda.stream(s):
+        out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
+        if bad is None:
+            bad = torch.zeros((S, n), dtype=torch.uint8, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    coder.scrub_crc_device(ptrs, strides, cells.shape[2], S, expected.data_ptr(), bad.data_ptr(), out.data_ptr(),
+                           checksum_type=checksum_type, stream=s.cuda_stream)
+    return out, bad
+
+
+def scrub_crc_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], expected, bad=None,
+                          checksum_type: int = CHECKSUM_CRC32C, stream=None, workspace=None):
+    """scrub_crc_batch for degraded stripes: present_masks[s] bit i = unit i of
+    stripe s is there (the other slots of cells and expected are not read).
+    -> (results, bad) as scrub_crc_batch, results as scrub_batch_mixed; the
+    present units of a stripe with k units or fewer are still verified.  Pass
+    `workspace` (uint8 cuda tensor of coder.scrub_crc_mixed_workspace_size(S)
+    bytes) to reuse one; it must stay untouched until the stream has passed
+    the call."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    with torch.cuda.stream(s):
+        out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
+        if bad is None:
+            bad = torch.zeros((S, n), dtype=torch.uint8, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    if workspace is None:
+        workspace = torch.empty(max(coder.scrub_crc_mixed_workspace_size(S), 1), dtype=torch.uint8,
+                                device=cells.device)
+        workspace.record_stream(s)
+    coder.scrub_crc_device_mixed(ptrs, strides, list(present_masks), cells.shape[2], S, expected.data_ptr(),
+                                 bad.data_ptr(), out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                 checksum_type=checksum_type, stream=s.cuda_stream)
+    return out, bad
 
 
 def decode_batch(coder: Coder, data, parity, missing: Sequence[int], out, stream=None) -> None:

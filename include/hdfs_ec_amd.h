@@ -507,6 +507,76 @@ int hec_scrub_device_mixed(hec_coder_t *coder, const uint8_t *const *d_shards, c
                            hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
                            void *hip_stream);
 
+/* Verified scrub: the two device calls above with the chunk checksums of every
+ * present unit verified in the same pass over the cells.  A block scanner
+ * exists to verify chunk sums, and the parity check exists to catch what sums
+ * cannot -- a unit whose sums were computed from the wrong bytes (HDFS-15759)
+ * -- so a scanner wants both answers for every stripe, and a repair worker
+ * wants them for the units hec_reconstruct_crc_device_mixed has just rebuilt
+ * and summed.  Shards, strides, present, survivors and extras, d_results, the
+ * workspace rules and status codes are those of hec_scrub_device /
+ * hec_scrub_device_mixed; the checksum buffers are those of
+ * hec_reconstruct_crc_device:
+ *   d_expected: [stripe][k+m][nck] big-endian u32, nck = ceil(cell_len /
+ *     bytes_per_checksum), 4-byte aligned; d_bad: [stripe][k+m] bytes.  Both
+ *     required with a checksum type other than HEC_CHECKSUM_NULL.
+ *   Results: d_results[stripes] holds exactly what hec_scrub_device /
+ *     hec_scrub_device_mixed return for the same cells and masks (missing-unit
+ *     bits and the (0, 0) of unchecked stripes included), zeroed by the call
+ *     itself on the stream (a zeroing kernel node under capture);
+ *     hec_scrub_verdict works unchanged.
+ *   Flags: every present unit of every stripe is verified against its
+ *     expected sums -- also in stripes with e == 0 (exactly k units present,
+ *     or fewer), whose parity result is (0, 0) but whose sums still have
+ *     something to check against.  A mismatch sets d_bad[s*(k+m) + unit] = 1;
+ *     flags are only ever set: the caller zeroes them, as for
+ *     hec_checksum_verify_device, whose flags over the present units these
+ *     are.  The cells and sums slots of missing units are never read.
+ *   The two outputs are independent of each other, and neither call writes to
+ *   the cells or to d_expected.  A flag does not always mean bad bytes: when
+ *   the sum itself is corrupt the parity verdict with the unit included is
+ *   CLEAN, and the caller may re-sum the unit instead of rebuilding it.
+ * Both calls are asynchronous on hip_stream: they never synchronise with the
+ * device, never allocate device memory and never read the flags back.
+ * HEC_CHECKSUM_NULL runs the plain scrub call and ignores the two checksum
+ * buffers; HEC_CHECKSUM_CRC32C and HEC_CHECKSUM_CRC32 are supported.
+ * HEC_ERR_DEVICE on a host-only coder.  HEC_ERR_INVALID_ARG, nothing queued:
+ * NULL coder, d_shards, shard_strides, d_results or (mixed form) present, a
+ * NULL d_shards[i], cell_len == 0, bytes_per_checksum == 0, misaligned
+ * d_results or d_expected, an unknown checksum type, NULL d_expected or d_bad
+ * with a checksum type other than NULL, and -- mixed form, when some stripe has
+ * a present unit -- a NULL, misaligned (16 B) or too small workspace.  HEC_OK,
+ * nothing queued: stripes == 0.
+ * One fused kernel (reads the k+e present cells of a stripe once) for k in
+ * {2,3,6,10}, 1 <= e <= 4 in every checked stripe, bytes_per_checksum == 512,
+ * 16-B aligned bases, strides and cell_len and plans whose first row has no
+ * zero; everything else runs, in stream order, a verify pass over the present
+ * units and the plain scrub call: the same results.
+ * hec_scrub_crc_device can be captured into a HIP graph on one stream (one
+ * zeroing node plus one kernel node, like hec_reconstruct_crc_device).
+ * The mixed form takes one launch per distinct presence mask, each over a
+ * device list of that mask's stripes (a mask with e == 0 and a present unit
+ * gets a sums-only launch): at most k+m+1 launches after one node failure, but
+ * a batch of many distinct masks pays a launch each.  The lists sit in
+ * d_workspace behind what hec_scrub_device_mixed keeps there
+ * (hec_scrub_crc_mixed_workspace_size bytes, 16-byte aligned; untouched until
+ * the stream reaches the work; calls in flight at once need different
+ * workspaces).  Capturing the mixed form into a HIP graph is not supported. */
+int hec_scrub_crc_device(hec_coder_t *coder, int checksum_type,
+                         const uint8_t *const *d_shards, const size_t *shard_strides,
+                         size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                         const uint8_t *d_expected, uint8_t *d_bad,
+                         hec_scrub_result_t *d_results, void *hip_stream);
+
+size_t hec_scrub_crc_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+int hec_scrub_crc_device_mixed(hec_coder_t *coder, int checksum_type,
+                               const uint8_t *const *d_shards, const size_t *shard_strides,
+                               const uint64_t *present, size_t cell_len, size_t stripes,
+                               size_t bytes_per_checksum,
+                               const uint8_t *d_expected, uint8_t *d_bad,
+                               hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
+                               void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

@@ -120,6 +120,16 @@ unsafe extern "C" {
     fn hec_scrub_device_mixed(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
                               present: *const u64, cell_len: usize, stripes: usize, d_results: *mut ScrubResult,
                               d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    fn hec_scrub_crc_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                            shard_strides: *const usize, cell_len: usize, stripes: usize,
+                            bytes_per_checksum: usize, d_expected: *const u8, d_bad: *mut u8,
+                            d_results: *mut ScrubResult, stream: *mut c_void) -> c_int;
+    fn hec_scrub_crc_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_scrub_crc_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                  shard_strides: *const usize, present: *const u64, cell_len: usize,
+                                  stripes: usize, bytes_per_checksum: usize, d_expected: *const u8,
+                                  d_bad: *mut u8, d_results: *mut ScrubResult, d_workspace: *mut c_void,
+                                  workspace_bytes: usize, stream: *mut c_void) -> c_int;
     fn hec_device_alloc(device: c_int, bytes: usize, flags: u32, out: *mut *mut c_void) -> c_int;
     fn hec_device_free(device: c_int, ptr: *mut c_void) -> c_int;
     fn hec_device_copy(device: c_int, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;
@@ -436,6 +446,57 @@ impl GpuCoder {
         check(unsafe {
             hec_scrub_device_mixed(self.raw, shards.as_ptr(), shard_strides.as_ptr(), present.as_ptr(), cell,
                                    present.len(), results, workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// `scrub_device` with the chunk checksums of every unit verified in the
+    /// same pass (`hec_scrub_crc_device`): `expected` is `[stripe][k+m][nck]`
+    /// big-endian u32 (4-byte aligned), `bad` is `[stripe][k+m]` flag bytes the
+    /// caller zeroes; a unit that does not match its sums gets its flag set.
+    /// `results` holds exactly what `scrub_device` returns; the two outputs are
+    /// independent.  A flagged unit whose stripe scrubs clean with the unit
+    /// included has a corrupt sum, not corrupt bytes.
+    ///
+    /// # Safety
+    /// As `scrub_device`; `expected` and `bad` valid for their layouts on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn scrub_crc_device(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                   cell: usize, stripes: usize, bytes_per_checksum: usize, expected: *const u8,
+                                   bad: *mut u8, results: *mut ScrubResult, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_crc_device(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(), cell,
+                                 stripes, bytes_per_checksum, expected, bad, results, stream)
+        })
+    }
+
+    /// Device bytes `scrub_crc_device_mixed` needs for `stripes` stripes.
+    pub fn scrub_crc_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_scrub_crc_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// `scrub_device_mixed` with the checksum buffers of `scrub_crc_device`
+    /// (`hec_scrub_crc_device_mixed`): every present unit of every stripe is
+    /// verified, also in stripes with k units or fewer; missing slots of the
+    /// cells and of `expected` are never read.  `workspace` is device memory of
+    /// `scrub_crc_mixed_workspace_size(stripes)` bytes (16-byte aligned),
+    /// untouched until `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `scrub_crc_device`; `workspace` valid for `workspace_bytes` on this device.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn scrub_crc_device_mixed(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                         present: &[u64], cell: usize, bytes_per_checksum: usize,
+                                         expected: *const u8, bad: *mut u8, results: *mut ScrubResult,
+                                         workspace: *mut c_void, workspace_bytes: usize,
+                                         stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_crc_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
+                                       present.as_ptr(), cell, present.len(), bytes_per_checksum, expected, bad,
+                                       results, workspace, workspace_bytes, stream)
         })
     }
 
