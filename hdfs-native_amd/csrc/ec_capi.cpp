@@ -1461,7 +1461,7 @@ int mixed_reconstruct_impl(hec_coder* c, const uint8_t* const* d_shards, const s
                        cell_len <= 0xFFFFFFFFull &&  // 32-bit lane offsets into a cell
                        aligned16(d_shards, shard_strides, unit_bits(n)) &&
                        aligned16(d_out, out_strides, batch.target_units) &&
-                       hec::reconstruct_mixed_resident(stripes, img.blob_bytes);
+                       hec::mixed_resident(stripes, img.blob_bytes);
     if (!fused) return per_run();
     if (!d_workspace || workspace_bytes < img.need) return HEC_ERR_INVALID_ARG;
     rc = upload_plan_image(c, batch, img, d_workspace, stream);
@@ -1685,7 +1685,7 @@ int hec_scrub_device_mixed(hec_coder_t* c, const uint8_t* const* d_shards, const
         a.results = reinterpret_cast<uint64_t*>(d_results);
         a.queue = reinterpret_cast<uint32_t*>(ws + img.queue_pos);
         if (!fast) return to_status(hec::launch_scrub_mixed_bytes(a, c->device, stream));
-        if (hec::scrub_mixed_resident(stripes, img.blob_bytes)) {
+        if (hec::mixed_resident(stripes, img.blob_bytes)) {
             const int lrc = hec::launch_scrub_mixed(a, int(batch.max_e), c->device, stream);
             if (lrc != -1) return to_status(lrc);
             // refused (the runtime would not grant the LDS): per run below

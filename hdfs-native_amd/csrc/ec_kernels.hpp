@@ -160,8 +160,11 @@ int launch_reconstruct_mixed(const ReconArgs& a, int rows, int device, hipStream
 // That budget: plan offsets (u32 per stripe, 16-B padded) + plan blob.  gfx950
 // has 160 KiB of LDS per CU and the kernel's static LDS is 1.5 KiB.
 constexpr uint64_t kReconResidentMax = 156u << 10;
-// True when a batch's plan offsets and blob fit it.
-bool reconstruct_mixed_resident(uint64_t stripes, uint64_t blob_bytes);
+// True when a batch's plan offsets and blob fit it (a uniform plan has no
+// offsets: stripes = 0); gf_scrub_mixed's budget is the same.
+inline bool mixed_resident(uint64_t stripes, uint64_t blob_bytes) {
+    return ((stripes * 4 + 15) & ~uint64_t(15)) + blob_bytes <= kReconResidentMax && blob_bytes % 4 == 0;
+}
 
 // ---- scrub: verify a stripe's parity and locate a corrupt unit --------------
 // Argument block of gf_scrub / gf_scrub_bytes (ec_scrub.hip).  Read-only over
@@ -226,12 +229,11 @@ struct ScrubMixedArgs {
 // Register kernel, plans resident in LDS: k in {2,3,6,10}, every stripe's
 // e <= max_e <= kMaxR, 16-B aligned bases, strides and cell_len, row 0 of every
 // plan without a zero (the caller checks).  With a.stripe_off the batch's
-// offsets + blob must fit the resident budget (scrub_mixed_resident) and
+// offsets + blob must fit the resident budget (mixed_resident) and
 // a.queue is required; without it (uniform plan) the one plan at a.plans is
 // resident and the tiles go in the fixed order.  0 ok, -1 unsupported (nothing
 // was launched), >0 hipError_t.
 int launch_scrub_mixed(const ScrubMixedArgs& a, int max_e, int device, hipStream_t stream);
-bool scrub_mixed_resident(uint64_t stripes, uint64_t blob_bytes);
 // Byte-granular kernel: any k <= kMaxK, e <= 16, alignment and cell_len; plans
 // with coefficient bytes, read from global memory.  Same results.
 int launch_scrub_mixed_bytes(const ScrubMixedArgs& a, int device, hipStream_t stream);

@@ -24,6 +24,7 @@
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "gf_device.hpp"
 #pragma clang diagnostic pop
+#include "launch_parts.hpp"
 
 namespace hec {
 
@@ -207,36 +208,19 @@ namespace {
 // Shapes of gf_decode_mixed: U = 4 chunks per lane in 256-thread blocks up to
 // k = 6, U = 2 in 512-thread blocks above; one round of wave-tiles per atomic
 // for k >= 6, four below (more atomics per byte there).
-template <int K, int R>
-const void* recon_fn() {
-    if constexpr (K > 6)
-        return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 2, 512, true, 1>);
-    else if constexpr (K == 6)
-        return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 4, 256, true, 1>);
-    else
-        return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 4, 256, true, 4>);
-}
-
-template <int K>
-const void* recon_pick_r(int r) {
-    switch (r) {
-        case 1: return recon_fn<K, 1>();
-        case 2: return recon_fn<K, 2>();
-        case 3: return recon_fn<K, 3>();
-        case 4: return recon_fn<K, 4>();
-        default: return nullptr;
+struct ReconFn {
+    template <int K, int R>
+    static const void* fn() {
+        if constexpr (K > 6)
+            return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 2, 512, true, 1>);
+        else if constexpr (K == 6)
+            return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 4, 256, true, 1>);
+        else
+            return reinterpret_cast<const void*>(&gf_reconstruct_mixed<K, R, 4, 256, true, 4>);
     }
-}
-
-// Dynamic LDS past 64 KiB (up to kReconResidentMax) needs the function
-// attribute, as in launch_decode_mixed.
-constexpr uint64_t kDynNoAttr = 64u << 10;
+};
 
 }  // namespace
-
-bool reconstruct_mixed_resident(uint64_t stripes, uint64_t blob_bytes) {
-    return ((stripes * 4 + 15) & ~uint64_t(15)) + blob_bytes <= kReconResidentMax && blob_bytes % 4 == 0;
-}
 
 int launch_reconstruct_mixed(const ReconArgs& in, int rows, int device, hipStream_t stream) {
     ReconArgs a = in;
@@ -244,43 +228,22 @@ int launch_reconstruct_mixed(const ReconArgs& in, int rows, int device, hipStrea
     if (a.cell_len % 16 != 0 || a.cell_len > 0xFFFFFFFFull || !a.queue || a.row0 < 0 ||
         a.row0 % kMaxR != 0 || a.row0 >= 16 || a.stripes > 0xFFFFFFFFull)
         return -1;
-    if (!reconstruct_mixed_resident(a.stripes, a.blob_bytes)) return -1;
-    const uint64_t dyn = ((a.stripes * 4 + 15) & ~uint64_t(15)) + a.blob_bytes;
-    const void* fn = nullptr;
-    switch (a.k) {
-        case 2: fn = recon_pick_r<2>(rows); break;
-        case 3: fn = recon_pick_r<3>(rows); break;
-        case 6: fn = recon_pick_r<6>(rows); break;
-        case 10: fn = recon_pick_r<10>(rows); break;
-        default: break;
-    }
-    if (!fn) return -1;
-    // The attribute is set to the resident ceiling, never to this launch's
-    // size (launch_decode_mixed: a coder may be shared by threads).
-    if (dyn > kDynNoAttr &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(kReconResidentMax)) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;  // the runtime refused the LDS: the caller launches per run of stripes
-    }
+    if (!mixed_resident(a.stripes, a.blob_bytes)) return -1;
+    const uint64_t dyn = resident_lds_bytes(a.stripes, a.blob_bytes);
+    const void* fn = pick_kr<ReconFn>(a.k, rows);
+    if (!fn || !set_resident_lds_attr(fn, dyn)) return -1;
     const Tune tn = tune_snapshot();
-    const int U = a.k > 6 ? 2 : 4, BS = a.k > 6 ? 512 : 256;
-    const uint64_t chunks = a.cell_len / 16;
-    const uint64_t tile = uint64_t(64) * U;  // wave-tiles
-    const uint64_t tps = (chunks + tile - 1) / tile;
-    const uint64_t total = tps * a.stripes;
-    if (total > 0xFFFFFFFFull) return -1;
+    if (!tile_geometry(a, 1024u * wave_tile_u(a.k))) return -1;
+    const uint64_t total = a.total_tiles;
     if (total == 0) return 0;
-    a.chunks = uint32_t(chunks);
-    a.tiles_per_stripe = uint32_t(tps);
-    a.total_tiles = uint32_t(total);
-    tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 4u, a.group, a.grouped_tiles);
+    set_tile_order(a, tn, 4u);
     a.drain = tn.drain == 1 ? 0u : 1u;
     // one block per CU: the resident plans are staged once per block and the
     // blocks drain the queue
     uint64_t grid = uint64_t(num_cus(device)) * (tn.blocks_per_cu ? tn.blocks_per_cu : 1);
     if (grid > total) grid = total;
     void* args[] = {&a};
-    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(BS), args, uint32_t(dyn), stream);
+    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(wave_tile_bs(a.k)), args, uint32_t(dyn), stream);
     return e == hipSuccess ? 0 : int(e);
 }
 

@@ -7,26 +7,25 @@
 // the registers that were just stored.  One pass of k reads + t writes where
 // verify + reconstruct + checksum make 2k reads + t writes + t reads.
 //
-// gf_reconstruct_crc is a sibling of gf_fused_crc's plain path
-// (ec_fused_kernel.hpp, the last branch of its tile loop): one input at a
-// time with the next one prefetched, the v_perm product tables of the launch's
-// coefficient rows, the fold checksum (scheme 12) over a wave-private 9-KiB
-// image of 144-B quarter rows, 256-thread blocks, two per CU.  It differs in
-// what is checksummed: the inputs only when VERIFY_IN (compared against the
-// expected sums), the outputs always (their sums stored), both addressed by
-// unit index in the engine's [stripe][k+m] layouts, and in an optional stripe
+// gf_reconstruct_crc has the shape of gf_fused_crc's plain path
+// (ec_fused_kernel.hpp): one input at a time with the next one prefetched,
+// 256-thread blocks, two per CU; the checksum rounds are crc_stage.hpp's.
+// Particular to it is what is checksummed: the inputs only when VERIFY_IN (compared against
+// the expected sums), the outputs always (their sums stored), both addressed
+// by unit index in the engine's [stripe][k+m] layouts, and an optional stripe
 // list, so a mixed batch takes one launch per distinct pattern.  Block tiles
 // in the fixed order: no counters, nothing to zero, capturable as is.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "ec_reconstruct_crc.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"
+#include "crc_stage.hpp"
 #include "ec_fused_kernel.hpp"
 #pragma clang diagnostic pop
+#include "launch_parts.hpp"
 
 namespace hec {
 
@@ -35,14 +34,11 @@ namespace hec {
 template <int K, int R, int SLABS, int KIND, bool VERIFY_IN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gf_reconstruct_crc(MatmulArgs a,
                                                                                                       ReconCrcArgs cs) {
-    static_assert(SLABS == 4 || SLABS == 8, "one or two cells per checksum round");
     static_assert(K > 0 && R >= 1 && R <= kMaxR, "compile-time k, 1..4 rows");
-    constexpr int SCHEME = 12;
-    using TL = crcdev::TableLayout<SCHEME>;
-    using Spec = crc::Spec<KIND>;
-    constexpr bool REFL = Spec::kReflected;
+    using Stage = CrcStage<SLABS, KIND>;
+    using TL = typename Stage::TL;
+    constexpr int SCHEME = Stage::SCHEME, STAGE = Stage::STAGE, SPR = Stage::SPR;
     constexpr int BS = 256, WAVES = BS / 64;
-    constexpr int PITCH = 144, STAGE = 64 * PITCH, SPR = 8 / SLABS;
     constexpr uint32_t WAVE_BYTES = SLABS * 1024u, TILE_BYTES = WAVES * WAVE_BYTES;
     constexpr bool PF = R * SLABS <= 24;  // register prefetch of the next survivor
     __shared__ PermTable s_tab[R][K];
@@ -101,48 +97,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const uint32_t sid = (SPR > 1 && sir > 0 && count > 1) ? cs.shard_id[first + 1] : cs.shard_id[first];
             return uint64_t(stripe) * cs.n_total + sid;
         };
-        // One round over the staged image: `count` cells starting at unit
-        // slot `first` of shard_id.  vin: survivors, compared against the
-        // expected sums; otherwise rebuilt units, their sums stored.
-        auto crc_round = [&](auto vin, int first, int count) {
-            constexpr bool VIN = decltype(vin)::value;
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-            const bool live_c = in_cell && sir < count;
-            uint32_t want = 0;
-            if (VIN && live_c && qi == 0)
-                want = exp_sums[sum_cell(first, count) * nck + cbyte / 512];  // issued before the lookups
-            uint32_t val = 0;
-            if (full && sir < count) {
-                uint32_t r = crcdev::quarter<SCHEME, REFL>(s_ctabs, stage + lane * PITCH, lane);
-                if (qi < 3) r = crcdev::shift_quarter<SCHEME>(s_ctabs, qi, r);
-                val = r;
-            } else if (live_c && qi == 0) {
-                // short last chunk of the cell: this lane walks it whole, bytewise
-                const uint32_t len = uint32_t(cell_len - cbyte);
-                uint32_t r = Spec::kInit;
-                for (uint32_t b = 0; b < len; b++)
-                    r = crcdev::byte_step<REFL, crcdev::ByteTable<SCHEME>::stride, crcdev::ByteTable<SCHEME>::bswap>(
-                        s_ctabs + crcdev::ByteTable<SCHEME>::off, r, stage[(lane + b / 128) * PITCH + (b % 128)]);
-                val = r ^ Spec::kXorout;
-            }
-            val ^= __shfl_xor(val, 1);
-            val ^= __shfl_xor(val, 2);
-            if (live_c && qi == 0) {
-                const uint32_t be = __builtin_bswap32(full ? (val ^ kfinal) : val);
-                if constexpr (VIN) {
-                    if (be != want) cs.bad[sum_cell(first, count)] = 1;
-                } else {
-                    out_sums[sum_cell(first, count) * nck + cbyte / 512] = be;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
+        const Stage crc{s_ctabs, stage, kfinal, cell_len, lane, qi, sir, cbyte, in_cell, full};
+        // `count` cells starting at unit slot `first` of shard_id.  Survivors:
+        // compared against the expected sums; rebuilt units: their sums stored.
+        auto verify_round = [&](int first, int count) {
+            crc.round(
+                count, [&] { return exp_sums[sum_cell(first, count) * nck + cbyte / 512]; },
+                [&](uint32_t sum, uint32_t want) {
+                    if (sum != want) cs.bad[sum_cell(first, count)] = 1;
+                });
         };
-        // slab u of the cell in round slot `slot`: lane l's 16 B -> row
-        // 8*(slot*SLABS + u) + l/8, byte 16*(l%8)
-        auto stage_piece = [&](int slot, int u, const u32x4& v) {
-            *reinterpret_cast<u32x4*>(stage + (8 * (slot * SLABS + u) + lane / 8) * PITCH + 16 * (lane % 8)) = v;
+        auto output_round = [&](int first, int count) {
+            crc.round(
+                count, [] { return 0u; },
+                [&](uint32_t sum, uint32_t) { out_sums[sum_cell(first, count) * nck + cbyte / 512] = sum; });
         };
         auto load_in = [&](int i, u32x4(&dst)[SLABS]) {
 #pragma unroll
@@ -163,7 +131,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (VERIFY_IN) {
 #pragma unroll
-                for (int u = 0; u < SLABS; u++) stage_piece(i % SPR, u, x[u]);
+                for (int u = 0; u < SLABS; u++) crc.put(i % SPR, u, x[u]);
             }
             // opaque per-input table offset threaded through the accumulators:
             // keeps the table reads (and the GF math) of input i from being
@@ -199,8 +167,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (VERIFY_IN) {
                 // a round once its SPR survivors are staged, or at the last one
-                if (i % SPR == SPR - 1 || i == K - 1)
-                    crc_round(std::true_type{}, i - i % SPR, i % SPR + 1);
+                if (i % SPR == SPR - 1 || i == K - 1) verify_round(i - i % SPR, i % SPR + 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (i + 1 < K) {
@@ -219,9 +186,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int u = 0; u < SLABS; u++) {
                 if (live[u])
                     store16<true>(a.out[j] + (uint64_t(stripe) * a.out_stride[j] + wbyte) + voff[u], acc[u][j]);
-                stage_piece(j % SPR, u, acc[u][j]);
+                crc.put(j % SPR, u, acc[u][j]);
             }
-            if (j % SPR == SPR - 1 || j == R - 1) crc_round(std::false_type{}, K + j - j % SPR, j % SPR + 1);
+            if (j % SPR == SPR - 1 || j == R - 1) output_round(K + j - j % SPR, j % SPR + 1);
         }
     }
 }
@@ -232,26 +199,17 @@ namespace {
 // r x 8 accumulators fit (k <= 6, r <= 3), else 4
 constexpr int recon_crc_slabs(int k, int r) { return (r <= 3 && k <= 6) ? 8 : 4; }
 
-template <int K, int R>
-const void* recon_crc_fn(int kind, bool verify_in) {
-    constexpr int SL = recon_crc_slabs(K, R);
-    if (kind == crc::kCrc32c)
-        return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, true>)
-                         : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, false>);
-    return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, true>)
-                     : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, false>);
-}
-
-template <int K>
-const void* recon_crc_pick_r(int r, int kind, bool verify_in) {
-    switch (r) {
-        case 1: return recon_crc_fn<K, 1>(kind, verify_in);
-        case 2: return recon_crc_fn<K, 2>(kind, verify_in);
-        case 3: return recon_crc_fn<K, 3>(kind, verify_in);
-        case 4: return recon_crc_fn<K, 4>(kind, verify_in);
-        default: return nullptr;
+struct ReconCrcFn {
+    template <int K, int R>
+    static const void* fn(int kind, bool verify_in) {
+        constexpr int SL = recon_crc_slabs(K, R);
+        if (kind == crc::kCrc32c)
+            return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, true>)
+                             : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCrc32c, false>);
+        return verify_in ? reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, true>)
+                         : reinterpret_cast<const void*>(&gf_reconstruct_crc<K, R, SL, crc::kCksum, false>);
     }
-}
+};
 
 }  // namespace
 
@@ -265,28 +223,15 @@ int launch_reconstruct_crc(const MatmulArgs& in, const ReconCrcArgs& cs, int dev
     for (int j = 0; j < a.r; j++)
         if (!a.out[j] || ((reinterpret_cast<uintptr_t>(a.out[j]) | a.out_stride[j]) & 15u)) return -1;
     const bool verify_in = cs.expected != nullptr;
-    const void* fn = nullptr;
-    switch (a.k) {
-        case 2: fn = recon_crc_pick_r<2>(a.r, cs.kind, verify_in); break;
-        case 3: fn = recon_crc_pick_r<3>(a.r, cs.kind, verify_in); break;
-        case 6: fn = recon_crc_pick_r<6>(a.r, cs.kind, verify_in); break;
-        case 10: fn = recon_crc_pick_r<10>(a.r, cs.kind, verify_in); break;
-        default: break;
-    }
+    const void* fn = pick_kr<ReconCrcFn>(a.k, a.r, cs.kind, verify_in);
     if (!fn) return -1;
     const Tune tn = tune_snapshot();
-    const uint64_t chunks = a.cell_len / 16;
-    const uint64_t tile_bytes = 1024u * uint64_t(recon_crc_slabs(a.k, a.r)) * 4u;  // 4 waves x SLABS KiB
-    const uint64_t tps = (a.cell_len + tile_bytes - 1) / tile_bytes;
-    const uint64_t total = tps * a.stripes;
-    if (chunks > 0xFFFFFFFFull || total > 0xFFFFFFFFull || a.stripes > 0xFFFFFFFFull) return -1;
+    if (!tile_geometry(a, 4096u * recon_crc_slabs(a.k, a.r))) return -1;
+    const uint64_t total = a.total_tiles;
     if (total == 0) return 0;
-    a.chunks = uint32_t(chunks);
-    a.tiles_per_stripe = uint32_t(tps);
-    a.total_tiles = uint32_t(total);
     // groups of 8 stripes and 32 blocks per CU (2 resident), as launch_fused's
     // block-tile case
-    tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 8u, a.group, a.grouped_tiles);
+    set_tile_order(a, tn, 8u);
     uint64_t grid = tn.grid ? uint64_t(tn.grid) : uint64_t(num_cus(device)) * 32;
     if (grid > total) grid = total;
     ReconCrcArgs c = cs;

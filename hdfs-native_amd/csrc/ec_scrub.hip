@@ -31,6 +31,7 @@
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "gf_device.hpp"
 #pragma clang diagnostic pop
+#include "launch_parts.hpp"
 #include "work_queue.hpp"
 
 namespace hec {
@@ -320,39 +321,20 @@ namespace {
 // default_wq in ec_kernels.hip): U = 4 in 256-thread blocks up to k = 6 (two
 // rounds of wave-tiles per atomic for k = 2, 3; one for k = 6), U = 2 in
 // 512-thread blocks and one round for k = 10.
-template <int K, int M>
-const void* scrub_fn(bool wq) {
-    if constexpr (K > 6)
-        return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 2, 512, 1>)
-                  : reinterpret_cast<const void*>(&gf_scrub<K, M, 2, 512, 0>);
-    else if constexpr (K == 6)
-        return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 1>)
-                  : reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 0>);
-    else
-        return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 2>)
-                  : reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 0>);
-}
-
-template <int K>
-const void* scrub_pick_m(int m, bool wq) {
-    switch (m) {
-        case 1: return scrub_fn<K, 1>(wq);
-        case 2: return scrub_fn<K, 2>(wq);
-        case 3: return scrub_fn<K, 3>(wq);
-        case 4: return scrub_fn<K, 4>(wq);
-        default: return nullptr;
+struct ScrubFn {
+    template <int K, int M>
+    static const void* fn(bool wq) {
+        if constexpr (K > 6)
+            return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 2, 512, 1>)
+                      : reinterpret_cast<const void*>(&gf_scrub<K, M, 2, 512, 0>);
+        else if constexpr (K == 6)
+            return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 1>)
+                      : reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 0>);
+        else
+            return wq ? reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 2>)
+                      : reinterpret_cast<const void*>(&gf_scrub<K, M, 4, 256, 0>);
     }
-}
-
-const void* scrub_pick(int k, int m, bool wq) {
-    switch (k) {
-        case 2: return scrub_pick_m<2>(m, wq);
-        case 3: return scrub_pick_m<3>(m, wq);
-        case 6: return scrub_pick_m<6>(m, wq);
-        case 10: return scrub_pick_m<10>(m, wq);
-        default: return nullptr;
-    }
-}
+};
 
 }  // namespace
 
@@ -371,20 +353,15 @@ int launch_scrub(const ScrubArgs& in, int device, hipStream_t stream) {
     // the fast kernel's minors pivot on P[0][t]; true for the shipped codecs
     // at these shapes, checked here for any matrix
     for (int t = 0; fast && t < a.k; t++) fast = a.coef[t] != 0;
-    const int U = a.k > 6 ? 2 : 4, BS = a.k > 6 ? 512 : 256;
-    const uint64_t chunks = a.cell_len / 16;
-    const uint64_t tps = (chunks + uint64_t(64) * U - 1) / (uint64_t(64) * U);
-    if (fast && tps * a.stripes > 0xFFF00000ull) fast = false;  // tile indices (+ the fixed order's stride) in 32 bits
+    // tile indices (+ the fixed order's stride) in 32 bits
+    if (fast && !tile_geometry(a, 1024u * wave_tile_u(a.k), 0xFFF00000ull)) fast = false;
     if (fast) {
         QueueLease lease = queue_lease(device, stream);  // empty: the fixed order
         a.queue = lease.use;
         a.queue_zero = lease.zero;
-        const void* fn = scrub_pick(a.k, a.m, bool(lease));
+        const void* fn = pick_kr<ScrubFn>(a.k, a.m, bool(lease));
         if (!fn) return -1;
-        a.chunks = uint32_t(chunks);
-        a.tiles_per_stripe = uint32_t(tps);
-        a.total_tiles = uint32_t(tps * a.stripes);
-        tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 4u, a.group, a.grouped_tiles);
+        set_tile_order(a, tn, 4u);
         a.drain = tn.drain == 1 ? 0u : 1u;
         // the queue: resident blocks only, each one drains it; the fixed
         // order: gf_matmul_v16's grids (8 blocks per CU for k = 10)
@@ -393,7 +370,7 @@ int launch_scrub(const ScrubArgs& in, int device, hipStream_t stream) {
         if (grid > a.total_tiles) grid = a.total_tiles;
         if (grid > 0xFFFFull) grid = 0xFFFF;
         void* args[] = {&a};
-        const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(BS), args, 0, stream);
+        const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(wave_tile_bs(a.k)), args, 0, stream);
         if (e != hipSuccess) return int(e);
         lease.launched();
         return 0;

@@ -6,22 +6,19 @@
 // for)?  One pass of k + e reads where hec_checksum_verify_device +
 // hec_scrub_device make 2 (k + e).
 //
-// gf_scrub_crc is a sibling of gf_reconstruct_crc<.., VERIFY_IN = true>
-// (ec_reconstruct_crc.hip): the same survivor loop -- one input at a time with
-// the next one prefetched, the v_perm product tables of the launch's rows of
-// G, the fold checksum (scheme 12) over a wave-private 9-KiB image of 144-B
-// quarter rows, a verify round against the expected sums -- and in the place
-// of its output rows the e extras, which are inputs too: loaded into the same
-// registers, staged and verified in the same rounds, and XORed into their
+// gf_scrub_crc has gf_reconstruct_crc<.., VERIFY_IN = true>'s survivor loop
+// (ec_reconstruct_crc.hip; the verify rounds are crc_stage.hpp's) and in the
+// place of its output rows the e extras, which are inputs too: loaded into the
+// same registers, staged and verified in the same rounds, and XORed into their
 // accumulator row, so the accumulators end as the syndromes
 //     s_j(b) = XOR_i G[j][i] * u_{S_i}(b)  ^  u_{E_j}(b),   j < e.
-// What follows is the tail of gf_scrub_mixed (ec_scrub_mixed.hip): one
-// OR-reduce and a ballot, a clean wave-tile writes nothing; otherwise bad
-// positions are counted, extras ruled out by "any other row non-zero",
-// survivors by the packed minors against row 0, and one lane sends two plain
-// 64-bit atomics.  Uniform plan per launch, optional stripe list, block tiles
-// in the fixed order: no counters, nothing to zero but the results,
-// capturable as is.
+// What follows is a register-lean form of gf_scrub_mixed's locate tail
+// (ec_scrub_mixed.hip): one OR-reduce and a ballot, a clean
+// wave-tile writes nothing; otherwise bad positions are counted, extras ruled
+// out by "any other row non-zero", survivors by the packed minors against row
+// 0, and one lane sends two plain 64-bit atomics.  Uniform plan per launch,
+// optional stripe list, block tiles in the fixed order: no counters, nothing
+// to zero but the results, capturable as is.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -31,8 +28,10 @@
 #include "ec_scrub_crc.hpp"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"
+#include "crc_stage.hpp"
 #include "ec_fused_kernel.hpp"
 #pragma clang diagnostic pop
+#include "launch_parts.hpp"
 
 namespace hec {
 
@@ -52,15 +51,12 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I..
 template <int K, int E, int SLABS, int KIND>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gf_scrub_crc(MatmulArgs a,
                                                                                                 ScrubCrcArgs cs) {
-    static_assert(SLABS == 4 || SLABS == 8, "one or two cells per checksum round");
     static_assert(K > 0 && E >= 1 && E <= kMaxR, "compile-time k, 1..4 checks");
     constexpr int N = K + E;  // cells read per stripe
-    constexpr int SCHEME = 12;
-    using TL = crcdev::TableLayout<SCHEME>;
-    using Spec = crc::Spec<KIND>;
-    constexpr bool REFL = Spec::kReflected;
+    using Stage = CrcStage<SLABS, KIND>;
+    using TL = typename Stage::TL;
+    constexpr int SCHEME = Stage::SCHEME, STAGE = Stage::STAGE, SPR = Stage::SPR;
     constexpr int BS = 256, WAVES = BS / 64;
-    constexpr int PITCH = 144, STAGE = 64 * PITCH, SPR = 8 / SLABS;
     constexpr uint32_t WAVE_BYTES = SLABS * 1024u, TILE_BYTES = WAVES * WAVE_BYTES;
     constexpr bool PF = E * SLABS <= 24;  // register prefetch of the next unit
     __shared__ PermTable s_tab[E][K];
@@ -117,42 +113,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const uint32_t sid = (SPR > 1 && sir > 0 && count > 1) ? cs.shard_id[first + 1] : cs.shard_id[first];
             return uint64_t(stripe) * cs.n_total + sid;
         };
-        // One round over the staged image: `count` cells starting at unit
-        // slot `first` of shard_id, compared against the expected sums.
-        auto crc_round = [&](int first, int count) {
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-            const bool live_c = in_cell && sir < count;
-            uint32_t want = 0;
-            if (live_c && qi == 0)
-                want = exp_sums[sum_cell(first, count) * nck + cbyte / 512];  // issued before the lookups
-            uint32_t val = 0;
-            if (full && sir < count) {
-                uint32_t r = crcdev::quarter<SCHEME, REFL>(s_ctabs, stage + lane * PITCH, lane);
-                if (qi < 3) r = crcdev::shift_quarter<SCHEME>(s_ctabs, qi, r);
-                val = r;
-            } else if (live_c && qi == 0) {
-                // short last chunk of the cell: this lane walks it whole, bytewise
-                const uint32_t len = uint32_t(cell_len - cbyte);
-                uint32_t r = Spec::kInit;
-                for (uint32_t b = 0; b < len; b++)
-                    r = crcdev::byte_step<REFL, crcdev::ByteTable<SCHEME>::stride, crcdev::ByteTable<SCHEME>::bswap>(
-                        s_ctabs + crcdev::ByteTable<SCHEME>::off, r, stage[(lane + b / 128) * PITCH + (b % 128)]);
-                val = r ^ Spec::kXorout;
-            }
-            val ^= __shfl_xor(val, 1);
-            val ^= __shfl_xor(val, 2);
-            if (live_c && qi == 0) {
-                const uint32_t be = __builtin_bswap32(full ? (val ^ kfinal) : val);
-                if (be != want) cs.bad[sum_cell(first, count)] = 1;
-            }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-        };
-        // slab u of the cell in round slot `slot`: lane l's 16 B -> row
-        // 8*(slot*SLABS + u) + l/8, byte 16*(l%8)
-        auto stage_piece = [&](int slot, int u, const u32x4& v) {
-            *reinterpret_cast<u32x4*>(stage + (8 * (slot * SLABS + u) + lane / 8) * PITCH + 16 * (lane % 8)) = v;
+        const Stage crc{s_ctabs, stage, kfinal, cell_len, lane, qi, sir, cbyte, in_cell, full};
+        // `count` cells starting at unit slot `first` of shard_id, compared
+        // against the expected sums
+        auto verify_round = [&](int first, int count) {
+            crc.round(
+                count, [&] { return exp_sums[sum_cell(first, count) * nck + cbyte / 512]; },
+                [&](uint32_t sum, uint32_t want) {
+                    if (sum != want) cs.bad[sum_cell(first, count)] = 1;
+                });
         };
         auto load_in = [&](int i, u32x4(&dst)[SLABS]) {
 #pragma unroll
@@ -176,7 +145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if constexpr (PF && i + 1 < N) load_in(i + 1, xn);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int u = 0; u < SLABS; u++) stage_piece(i % SPR, u, x[u]);
+            for (int u = 0; u < SLABS; u++) crc.put(i % SPR, u, x[u]);
             if constexpr (i < K) {
                 // opaque per-input table offset threaded through the
                 // accumulators: keeps the table reads (and the GF math) of
@@ -216,7 +185,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
             __builtin_amdgcn_sched_barrier(0);
             // a round once its SPR units are staged, or at the last one
-            if constexpr (i % SPR == SPR - 1 || i == N - 1) crc_round(i - i % SPR, i % SPR + 1);
+            if constexpr (i % SPR == SPR - 1 || i == N - 1) verify_round(i - i % SPR, i % SPR + 1);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (i + 1 < N) {
                 if constexpr (PF) {
@@ -339,23 +308,14 @@ namespace {
 // keeps them
 constexpr int scrub_crc_slabs(int k, int e) { return (e == 1 && k <= 6) ? 8 : 4; }
 
-template <int K, int E>
-const void* scrub_crc_fn(int kind) {
-    constexpr int SL = scrub_crc_slabs(K, E);
-    if (kind == crc::kCrc32c) return reinterpret_cast<const void*>(&gf_scrub_crc<K, E, SL, crc::kCrc32c>);
-    return reinterpret_cast<const void*>(&gf_scrub_crc<K, E, SL, crc::kCksum>);
-}
-
-template <int K>
-const void* scrub_crc_pick_e(int e, int kind) {
-    switch (e) {
-        case 1: return scrub_crc_fn<K, 1>(kind);
-        case 2: return scrub_crc_fn<K, 2>(kind);
-        case 3: return scrub_crc_fn<K, 3>(kind);
-        case 4: return scrub_crc_fn<K, 4>(kind);
-        default: return nullptr;
+struct ScrubCrcFn {
+    template <int K, int E>
+    static const void* fn(int kind) {
+        constexpr int SL = scrub_crc_slabs(K, E);
+        if (kind == crc::kCrc32c) return reinterpret_cast<const void*>(&gf_scrub_crc<K, E, SL, crc::kCrc32c>);
+        return reinterpret_cast<const void*>(&gf_scrub_crc<K, E, SL, crc::kCksum>);
     }
-}
+};
 
 }  // namespace
 
@@ -372,31 +332,18 @@ int launch_scrub_crc(const MatmulArgs& in, const ScrubCrcArgs& cs, int device, h
             return -1;
     for (int i = 0; i < a.k; i++)
         if (a.coef[i] == 0) return -1;  // the minors divide by row 0
-    const void* fn = nullptr;
-    switch (a.k) {
-        case 2: fn = scrub_crc_pick_e<2>(a.r, cs.kind); break;
-        case 3: fn = scrub_crc_pick_e<3>(a.r, cs.kind); break;
-        case 6: fn = scrub_crc_pick_e<6>(a.r, cs.kind); break;
-        case 10: fn = scrub_crc_pick_e<10>(a.r, cs.kind); break;
-        default: break;
-    }
+    const void* fn = pick_kr<ScrubCrcFn>(a.k, a.r, cs.kind);
     if (!fn) return -1;
     const Tune tn = tune_snapshot();
-    const uint64_t chunks = a.cell_len / 16;
-    const uint64_t tile_bytes = 1024u * uint64_t(scrub_crc_slabs(a.k, a.r)) * 4u;  // 4 waves x SLABS KiB
-    const uint64_t tps = (a.cell_len + tile_bytes - 1) / tile_bytes;
-    const uint64_t total = tps * a.stripes;
-    if (chunks > 0xFFFFFFFFull || total > 0xFFFFFFFFull || a.stripes > 0xFFFFFFFFull) return -1;
+    if (!tile_geometry(a, 4096u * scrub_crc_slabs(a.k, a.r))) return -1;
+    const uint64_t total = a.total_tiles;
     if (total == 0) return 0;
-    a.chunks = uint32_t(chunks);
-    a.tiles_per_stripe = uint32_t(tps);
-    a.total_tiles = uint32_t(total);
     // groups of 8 stripes as launch_reconstruct_crc, but 4 blocks per CU (2
     // resident) where it takes 32, and only the resident 2 for a launch over
     // a stripe list: a mixed batch is one launch per mask over a ninth or a
     // fourteenth of the stripes, and with 32 most blocks staged their tables
     // for a single tile (measured: DESIGN.md 3.4f)
-    tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 8u, a.group, a.grouped_tiles);
+    set_tile_order(a, tn, 8u);
     uint64_t grid = tn.grid ? uint64_t(tn.grid) : uint64_t(num_cus(device)) * (cs.stripe_list ? 2 : 4);
     if (grid > total) grid = total;
     ScrubCrcArgs c = cs;

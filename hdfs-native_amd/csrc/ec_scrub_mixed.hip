@@ -33,6 +33,7 @@
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "gf_device.hpp"
 #pragma clang diagnostic pop
+#include "launch_parts.hpp"
 
 namespace hec {
 
@@ -412,39 +413,22 @@ namespace {
 // Shapes of gf_reconstruct_mixed: U = 4 chunks per lane in 256-thread blocks
 // up to k = 6, U = 2 in 512-thread blocks above; one round of wave-tiles per
 // atomic for k >= 6, four below.
-template <int K, int M>
-const void* scrub_mixed_fn(bool wq) {
-    if constexpr (K > 6)
-        return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 2, 512, 1>)
-                  : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 2, 512, 0>);
-    else if constexpr (K == 6)
-        return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 1>)
-                  : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 0>);
-    else
-        return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 4>)
-                  : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 0>);
-}
-
-template <int K>
-const void* scrub_mixed_pick_m(int m, bool wq) {
-    switch (m) {
-        case 1: return scrub_mixed_fn<K, 1>(wq);
-        case 2: return scrub_mixed_fn<K, 2>(wq);
-        case 3: return scrub_mixed_fn<K, 3>(wq);
-        case 4: return scrub_mixed_fn<K, 4>(wq);
-        default: return nullptr;
+struct ScrubMixedFn {
+    template <int K, int M>
+    static const void* fn(bool wq) {
+        if constexpr (K > 6)
+            return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 2, 512, 1>)
+                      : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 2, 512, 0>);
+        else if constexpr (K == 6)
+            return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 1>)
+                      : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 0>);
+        else
+            return wq ? reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 4>)
+                      : reinterpret_cast<const void*>(&gf_scrub_mixed<K, M, 4, 256, 0>);
     }
-}
-
-// Dynamic LDS past 64 KiB (up to kReconResidentMax) needs the function
-// attribute, as in launch_reconstruct_mixed.
-constexpr uint64_t kScrubDynNoAttr = 64u << 10;
+};
 
 }  // namespace
-
-bool scrub_mixed_resident(uint64_t stripes, uint64_t blob_bytes) {
-    return ((stripes * 4 + 15) & ~uint64_t(15)) + blob_bytes <= kReconResidentMax && blob_bytes % 4 == 0;
-}
 
 int launch_scrub_mixed(const ScrubMixedArgs& in, int max_e, int device, hipStream_t stream) {
     ScrubMixedArgs a = in;
@@ -454,35 +438,15 @@ int launch_scrub_mixed(const ScrubMixedArgs& in, int max_e, int device, hipStrea
         !a.results || !a.plans || (!uniform && !a.queue))
         return -1;
     if (a.stripes == 0) return 0;
-    if (!scrub_mixed_resident(uniform ? 0 : a.stripes, a.blob_bytes)) return -1;
-    const uint64_t dyn = (uniform ? 0 : ((a.stripes * 4 + 15) & ~uint64_t(15))) + a.blob_bytes;
-    const void* fn = nullptr;
-    switch (a.k) {
-        case 2: fn = scrub_mixed_pick_m<2>(max_e, !uniform); break;
-        case 3: fn = scrub_mixed_pick_m<3>(max_e, !uniform); break;
-        case 6: fn = scrub_mixed_pick_m<6>(max_e, !uniform); break;
-        case 10: fn = scrub_mixed_pick_m<10>(max_e, !uniform); break;
-        default: break;
-    }
-    if (!fn) return -1;
-    // The attribute is set to the resident ceiling, never to this launch's
-    // size (a coder may be shared by threads).
-    if (dyn > kScrubDynNoAttr &&
-        hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(kReconResidentMax)) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;  // the runtime refused the LDS: the caller launches per run of stripes
-    }
+    if (!mixed_resident(uniform ? 0 : a.stripes, a.blob_bytes)) return -1;
+    const uint64_t dyn = resident_lds_bytes(uniform ? 0 : a.stripes, a.blob_bytes);
+    const void* fn = pick_kr<ScrubMixedFn>(a.k, max_e, !uniform);
+    if (!fn || !set_resident_lds_attr(fn, dyn)) return -1;
     const Tune tn = tune_snapshot();
-    const int U = a.k > 6 ? 2 : 4, BS = a.k > 6 ? 512 : 256;
-    const uint64_t chunks = a.cell_len / 16;
-    const uint64_t tile = uint64_t(64) * U;  // wave-tiles
-    const uint64_t tps = (chunks + tile - 1) / tile;
-    const uint64_t total = tps * a.stripes;
-    if (total > 0xFFF00000ull) return -1;  // tile indices (+ the fixed order's stride) in 32 bits
-    a.chunks = uint32_t(chunks);
-    a.tiles_per_stripe = uint32_t(tps);
-    a.total_tiles = uint32_t(total);
-    tile_order(a.stripes, a.tiles_per_stripe, tn.group > 0 ? uint32_t(tn.group) : 4u, a.group, a.grouped_tiles);
+    // tile indices (+ the fixed order's stride) in 32 bits
+    if (!tile_geometry(a, 1024u * wave_tile_u(a.k), 0xFFF00000ull)) return -1;
+    const uint64_t total = a.total_tiles;
+    set_tile_order(a, tn, 4u);
     a.drain = tn.drain == 1 ? 0u : 1u;
     if (uniform) a.queue = nullptr;
     // one block per CU: the resident plans are staged once per block
@@ -490,7 +454,7 @@ int launch_scrub_mixed(const ScrubMixedArgs& in, int max_e, int device, hipStrea
     if (grid > total) grid = total;
     if (grid > 0xFFFFull) grid = 0xFFFF;
     void* args[] = {&a};
-    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(BS), args, uint32_t(dyn), stream);
+    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(wave_tile_bs(a.k)), args, uint32_t(dyn), stream);
     return e == hipSuccess ? 0 : int(e);
 }
 

@@ -46,7 +46,11 @@ def main():
     # shape, where a wave's tile + fx_step is still inside the batch
     big_s, big_cell = loop_shape(6)
     scrubs = [("xor", 2, 1, S, TILE[2] + 16), ("rs", 3, 2, S, TILE[3] + 16), ("rs", 6, 3, S, TILE[6] + 16),
-              ("rs", 10, 4, S, TILE[10] + 16), ("xor", 6, 1, S, TILE[6] + 16), ("rs", 6, 3, big_s, big_cell)]
+              ("rs", 10, 4, S, TILE[10] + 16), ("xor", 6, 1, S, TILE[6] + 16)]
+    # the other (k, m) the register kernel is built for: one wave-tile + a short chunk
+    scrubs += [("rs", k, m, S, TILE[k] + 16) for k in (2, 3, 6, 10) for m in (1, 2, 3, 4)
+               if (k, m) not in {(2, 1), (3, 2), (6, 3), (10, 4), (6, 1)}]
+    scrubs += [("rs", 6, 3, big_s, big_cell)]
     s_img, s_want = [[], []], [[], []]  # per replay: numpy images, expected results
     for x, (codec, k, m, stripes, cell) in enumerate(scrubs):
         clean = consistent_stripes(codec, k, m, stripes, cell)

@@ -277,6 +277,26 @@ def test_mixed_rs104(dev):
     assert torch.equal(buf, expected)
 
 
+KERNEL_SHAPES = [(k, r) for k in (2, 3, 6, 10) for r in (1, 2, 3, 4)]
+
+
+@pytest.mark.parametrize("k,r", KERNEL_SHAPES, ids=[f"k{k}-r{r}" for k, r in KERNEL_SHAPES])
+def test_mixed_every_kernel_shape(dev, k, r):
+    """gf_reconstruct_mixed<K, R> at every (K, R) it is built for: RS(k,4), every
+    stripe of the batch loses exactly r units (so the launch has r rows), data
+    and parity among them; 528 B = 33 chunks in one wave-tile, 9232 B = a short
+    last wave-tile."""
+    m, S = 4, 4
+    rng = np.random.default_rng(100 * k + r)
+    for cell in (528, 9232):
+        losts = [tuple(sorted(rng.choice(k + m, size=r, replace=False).tolist())) for _ in range(S)]
+        losts[0] = tuple(range(r))                   # data units only (k = 2: data, then parity)
+        losts[1] = tuple(range(k + m - r, k + m))    # parity units only
+        buf, expected = mixed_in_place(coder(k, m), truth(k, m, S, cell), losts, dev)
+        torch.cuda.synchronize()
+        assert torch.equal(buf, expected), (cell, losts)
+
+
 def test_mixed_rs66_two_launches(dev):
     """RS(6,6) with 5 and 6 units lost per stripe: more than 4 target rows, so
     a second launch with row0 = 4 (the header's second word of target bytes)."""

@@ -368,6 +368,33 @@ def test_uniform_without_expected(dev, cell):
     c.check()
 
 
+KERNEL_SHAPES = [(k, r) for k in (2, 3, 6, 10) for r in (1, 2, 3, 4)]
+
+
+@pytest.mark.parametrize("k,r", KERNEL_SHAPES, ids=[f"k{k}-r{r}" for k, r in KERNEL_SHAPES])
+def test_every_kernel_shape(dev, k, r):
+    """gf_reconstruct_crc<K, R, .., KIND, VERIFY_IN> at every (K, R) it is built
+    for, both checksum types, with and without d_expected: RS(k,4) with r units
+    lost, data and parity among them.  528 B = one full chunk and a 16-B short
+    one, 9232 B = a short last tile; with d_expected a survivor of stripe 1 has
+    a corrupt byte in its last 16 B and must be the one flag."""
+    m, S = 4, 3
+    lost = tuple(range(k - (r + 1) // 2, k + r // 2))  # the last data units and the first parity units
+    surv = [i for i in range(k + m) if i not in lost][:k]
+    cases = []
+    for cell in (528, 9232):
+        for ctype in (C32C, C32):
+            cases.append(uniform_case(coder(k, m), k, m, S, cell, lost, dev, ctype=ctype,
+                                      corrupt=[(1, surv[-1], cell - 5)]))
+            cases.append(uniform_case(coder(k, m), k, m, S, cell, lost, dev, ctype=ctype, expected=None))
+    for c in cases:
+        c.uniform()
+    torch.cuda.synchronize()
+    for c in cases:
+        assert c.dirty == ({1} if c.expected is not None else set())
+        c.check((c.cell, c.ctype, c.expected is not None))
+
+
 # ---- 4. verification ------------------------------------------------------------
 
 @pytest.mark.parametrize("form", ["uniform", "mixed"])

@@ -8,7 +8,7 @@ lands on the wrong stripe or a lane past the cell that is counted shows as
 well as a wrong mask.  Every result buffer is handed in filled with 0xFF: the
 call zeroes it itself.
 
-Which kernel each group of tests reaches (scrub_pick in csrc/ec_scrub.hip
+Which kernel each group of tests reaches (ScrubFn in csrc/ec_scrub.hip
 builds gf_scrub<K, M, U, BS, WQ> for K in {2, 3, 6, 10} x M in {1, 2, 3, 4},
 each with the work queue, WQ > 0, and in the fixed tile order, WQ == 0; a
 kernel added there gets its row here):
@@ -38,8 +38,8 @@ kernel added there gets its row here):
                                                   counter sets of three streams
     test_graph_capture_replay                   gf_scrub<6,3> and <10,4>, WQ > 0 on
                                                   graph counter sets
-    test_fixed_tile_order_in_child_process      gf_scrub<2,1 / 3,2 / 6,3 / 10,4 /
-      (scrub_fixed_order_child.py)                6,1, WQ == 0> and the fixed-order
+    test_fixed_tile_order_in_child_process      gf_scrub<K, M, WQ == 0>, all 16
+      (scrub_fixed_order_child.py)                (K, M), and the fixed-order
                                                   gf_matmul kernels behind encode,
                                                   decode and reconstruct, once the
                                                   graph pool is used up

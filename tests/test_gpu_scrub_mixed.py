@@ -6,7 +6,7 @@ exactly.  Every result buffer is handed in filled with 0xFF (the call zeroes it
 itself) and the slots a stripe lacks are filled with random garbage, so a
 kernel that reads them shows.
 
-Which kernel each test reaches (scrub_mixed_fn in csrc/ec_scrub_mixed.hip builds
+Which kernel each test reaches (ScrubMixedFn in csrc/ec_scrub_mixed.hip builds
 gf_scrub_mixed<K, M, U, BS, WQ> for K in {2, 3, 6, 10} x M in {1, 2, 3, 4}: WQ > 0
 with the batch's plans resident in LDS, WQ == 0 for the uniform-plan launches
 of a batch whose plans overflow it; M is the largest e of the batch):
