@@ -982,6 +982,16 @@ int resolve_reconstruct(hec_coder* c, const uint8_t* const* units, const uint8_t
     return HEC_OK;
 }
 
+// The rows a mixed decode needs for one presence mask: the missing data
+// units, which lead the plan's `lost`.
+int decode_rows(hec_coder* c, uint64_t mask, RowPlan* rp) {
+    rp->plan = plan_of_mask(c, mask);
+    if (rp->plan->status != HEC_OK) return rp->plan->status;
+    rp->rows.resize(rp->plan->missing.size());
+    std::iota(rp->rows.begin(), rp->rows.end(), size_t(0));
+    return HEC_OK;
+}
+
 // The rows a mixed reconstruction needs for one (presence, want) pattern.
 int reconstruct_rows(hec_coder* c, uint64_t mask, uint64_t wmask, RowPlan* rp) {
     if (!wmask) return HEC_OK;
@@ -1247,19 +1257,23 @@ PlanImage plan_image(const Batch& b, size_t k, bool tables, size_t queue_bytes) 
     return img;
 }
 
-// Writes the image (every byte of img.need: offsets, entries, zeroes in the
-// pads and the counters) and queues its upload to d_workspace.
+// Writes the image: every byte of img.need (offsets, entries, zeroes in the
+// pads and the counters).
+void write_plan_image(uint8_t* host, const Batch& b, const PlanImage& img, size_t k) {
+    const size_t stripes = b.stripe_plan.size(), blob_end = img.blob_pos + img.blob_bytes;
+    uint32_t* soff = reinterpret_cast<uint32_t*>(host);
+    for (size_t s = 0; s < stripes; s++)
+        soff[s] = b.stripe_plan[s] == kNoPlanId ? hec::kNoPlan : img.plan_off[b.stripe_plan[s]];
+    std::memset(host + stripes * sizeof(uint32_t), 0, img.blob_pos - stripes * sizeof(uint32_t));
+    for (size_t pi = 0; pi < b.plans.size(); pi++)
+        write_plan_entry(host + img.blob_pos + img.plan_off[pi], k, b.plans[pi], img.tables);
+    std::memset(host + blob_end, 0, img.need - blob_end);
+}
+
+// Writes the image and queues its upload to d_workspace.
 int upload_plan_image(hec_coder* c, const Batch& b, const PlanImage& img, void* d_workspace, hipStream_t stream) {
-    return upload_pinned(c, img.need, d_workspace, stream, [&](uint8_t* host) {
-        const size_t stripes = b.stripe_plan.size(), blob_end = img.blob_pos + img.blob_bytes;
-        uint32_t* soff = reinterpret_cast<uint32_t*>(host);
-        for (size_t s = 0; s < stripes; s++)
-            soff[s] = b.stripe_plan[s] == kNoPlanId ? hec::kNoPlan : img.plan_off[b.stripe_plan[s]];
-        std::memset(host + stripes * sizeof(uint32_t), 0, img.blob_pos - stripes * sizeof(uint32_t));
-        for (size_t pi = 0; pi < b.plans.size(); pi++)
-            write_plan_entry(host + img.blob_pos + img.plan_off[pi], c->k, b.plans[pi], img.tables);
-        std::memset(host + blob_end, 0, img.need - blob_end);
-    });
+    return upload_pinned(c, img.need, d_workspace, stream,
+                         [&](uint8_t* host) { write_plan_image(host, b, img, c->k); });
 }
 
 // What hec::MixedArgs, hec::ReconArgs and hec::ScrubMixedArgs share.
@@ -1312,19 +1326,11 @@ int mixed_decode_impl(hec_coder* c, const uint8_t* const* d_shards, const size_t
                       uint8_t* const* d_out, const size_t* out_strides, const uint64_t* present, size_t cell_len,
                       size_t stripes, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
     const size_t k = c->k, n = c->k + c->m;
-    // 1. plan per distinct mask (host), fail before launching anything: the
-    // missing data units, which lead the plan's `lost`
+    // 1. plan per distinct mask (host), fail before launching anything
     Batch batch;
     int rc = group_stripes(
         c, present, stripes, 0xFFFF, [](size_t, uint64_t) { return uint64_t(0); },
-        [&](uint64_t mask, uint64_t, RowPlan* rp) {
-            rp->plan = plan_of_mask(c, mask);
-            if (rp->plan->status != HEC_OK) return rp->plan->status;
-            rp->rows.resize(rp->plan->missing.size());
-            std::iota(rp->rows.begin(), rp->rows.end(), size_t(0));
-            return int(HEC_OK);
-        },
-        &batch);
+        [&](uint64_t mask, uint64_t, RowPlan* rp) { return decode_rows(c, mask, rp); }, &batch);
     if (rc != HEC_OK) return rc;
     if (batch.plans.empty()) return HEC_OK;
     if (any_null(d_out, batch.target_units)) return HEC_ERR_INVALID_ARG;
