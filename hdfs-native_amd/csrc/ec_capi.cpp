@@ -35,6 +35,7 @@
 #include "../../include/hdfs_ec_amd_exp.h"
 #include "checksum.hpp"
 #include "checksum_tables.hpp"
+#include "crc_compose.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
 #include "ec_scrub_crc.hpp"
@@ -2172,6 +2173,65 @@ int hec_checksum_verify_device(hec_coder_t* c, int checksum_type, const uint8_t*
     if (!d_expected || !d_bad) return HEC_ERR_INVALID_ARG;
     return checksum_entry(c, checksum_type, d_bases, strides, n_shards, cell_len, stripes, bytes_per_checksum,
                           nullptr, d_expected, d_bad, hip_stream);
+}
+
+// ---- Composite CRCs (crc_compose.hpp): cell, unit and group sums from chunk sums ----
+
+int hec_crc_concat(int checksum_type, uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t* out) {
+    const int kind = crc_kind(checksum_type);
+    if (kind < 0 || !out) return HEC_ERR_INVALID_ARG;
+    *out = kind == hec::crc::kCrc32c ? hec::crc::concat<hec::crc::kCrc32c>(crc_a, crc_b, len_b)
+                                     : hec::crc::concat<hec::crc::kCksum>(crc_a, crc_b, len_b);
+    return HEC_OK;
+}
+
+int hec_composite_crc(int checksum_type, const uint8_t* sums, size_t n_units, size_t data_units, size_t cell_len,
+                      size_t stripes, size_t bytes_per_checksum, uint64_t data_len, uint8_t* cell_crcs,
+                      uint8_t* unit_crcs, uint8_t* group_crc) {
+    const int kind = crc_kind(checksum_type);
+    hec::crc::Geometry g;
+    if (kind < 0 || !sums ||
+        !hec::crc::make_geometry(n_units, data_units, cell_len, stripes, bytes_per_checksum, data_len, &g))
+        return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    return guarded([&] {
+        if (kind == hec::crc::kCrc32c)
+            hec::crc::composite_host<hec::crc::kCrc32c>(g, sums, cell_crcs, unit_crcs, group_crc);
+        else
+            hec::crc::composite_host<hec::crc::kCksum>(g, sums, cell_crcs, unit_crcs, group_crc);
+        return int(HEC_OK);
+    });
+}
+
+size_t hec_composite_crc_workspace_size(size_t n_units, size_t stripes) {
+    if (n_units < 1 || n_units > hec::crc::kComposeMaxUnits) return 0;
+    return size_t(hec::crc::compose_workspace_bytes(n_units, stripes));
+}
+
+int hec_composite_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* d_sums, size_t n_units,
+                             size_t data_units, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                             uint64_t data_len, uint8_t* d_cell_crcs, uint8_t* d_unit_crcs, uint8_t* d_group_crc,
+                             void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_composite_crc_device");
+    const int kind = crc_kind(checksum_type);
+    hec::crc::Geometry g;
+    const uintptr_t align = reinterpret_cast<uintptr_t>(d_sums) | reinterpret_cast<uintptr_t>(d_cell_crcs) |
+                            reinterpret_cast<uintptr_t>(d_unit_crcs) | reinterpret_cast<uintptr_t>(d_group_crc);
+    if (!c || !d_sums || kind < 0 || (align & 3u) ||
+        !hec::crc::make_geometry(n_units, data_units, cell_len, stripes, bytes_per_checksum, data_len, &g))
+        return HEC_ERR_INVALID_ARG;
+    if (stripes == 0 || (!d_cell_crcs && !d_unit_crcs && !d_group_crc)) return HEC_OK;
+    if ((d_unit_crcs || d_group_crc) &&
+        (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) ||
+         workspace_bytes < hec::crc::compose_workspace_bytes(n_units, stripes)))
+        return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const int rc = hec::launch_composite_crc(kind, g, d_sums, d_cell_crcs, d_unit_crcs, d_group_crc, d_workspace,
+                                                 c->device, static_cast<hipStream_t>(hip_stream));
+        return rc == 0 ? int(HEC_OK) : to_status(rc);
+    });
 }
 
 int hec_encode_crc_device(hec_coder_t* c, const uint8_t* const* d_data, const size_t* data_strides,

@@ -50,6 +50,35 @@ inline void check(int rc) {
     }
 }
 
+// Composite CRCs on the host (no coder, no GPU): crc(A || B) from crc(A),
+// crc(B) and |B|, and the cell / unit / group CRCs of a block group from its
+// [stripe][n_units][nck] big-endian chunk sums (data_len == 0: every stripe full).
+inline uint32_t crc_concat(int checksum_type, uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+    uint32_t out = 0;
+    check(hec_crc_concat(checksum_type, crc_a, crc_b, len_b, &out));
+    return out;
+}
+struct CompositeCrc {
+    std::vector<uint32_t> cells;  // [stripes][n_units]
+    std::vector<uint32_t> units;  // [n_units]
+    uint32_t group = 0;
+};
+inline CompositeCrc composite_crc(int checksum_type, const uint8_t* sums, size_t n_units, size_t data_units,
+                                  size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len = 0) {
+    Bytes cells(4 * stripes * n_units + 1), units(4 * n_units + 1), group(4);
+    check(hec_composite_crc(checksum_type, sums, n_units, data_units, cell_len, stripes, bytes_per_checksum, data_len,
+                            cells.data(), units.data(), group.data()));
+    auto word = [](const uint8_t* p) { return uint32_t(p[0]) << 24 | uint32_t(p[1]) << 16 | uint32_t(p[2]) << 8 | p[3]; };
+    CompositeCrc out;
+    for (size_t i = 0; i < stripes * n_units; i++) out.cells.push_back(word(&cells[4 * i]));
+    for (size_t i = 0; i < n_units; i++) out.units.push_back(word(&units[4 * i]));
+    out.group = stripes ? word(group.data()) : 0;
+    return out;
+}
+inline size_t composite_crc_workspace_size(size_t n_units, size_t stripes) {
+    return hec_composite_crc_workspace_size(n_units, stripes);
+}
+
 // gf256.rs:25-138 on one MI355X.
 class Coder {
    public:
@@ -243,6 +272,18 @@ class Coder {
             throw std::invalid_argument("scrub_crc_device: need data_units + parity_units units");
         check(hec_scrub_crc_device(h_.get(), checksum_type, d_units.data(), strides.data(), cell_len, stripes,
                                    bytes_per_checksum, d_expected, d_bad, d_results, hip_stream));
+    }
+    // Composite CRCs on the device (hec_composite_crc_device): cell, unit and
+    // group CRCs, each optional, from the [stripe][n_units][nck] chunk sums at
+    // d_sums; d_workspace of composite_crc_workspace_size(n_units, stripes)
+    // bytes for the unit and group outputs.
+    void composite_crc_device(int checksum_type, const uint8_t* d_sums, size_t n_units, size_t data_units,
+                              size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                              uint8_t* d_cell_crcs, uint8_t* d_unit_crcs, uint8_t* d_group_crc, void* d_workspace,
+                              size_t workspace_bytes, void* hip_stream = nullptr) const {
+        check(hec_composite_crc_device(h_.get(), checksum_type, d_sums, n_units, data_units, cell_len, stripes,
+                                       bytes_per_checksum, data_len, d_cell_crcs, d_unit_crcs, d_group_crc,
+                                       d_workspace, workspace_bytes, hip_stream));
     }
     // One presence mask per stripe (hec_scrub_crc_device_mixed): only present
     // units are read and verified, also where k units or fewer are present;

@@ -68,6 +68,7 @@ EXPORTS = [
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
+    "hec_crc_concat", "hec_composite_crc", "hec_composite_crc_workspace_size", "hec_composite_crc_device",
 ]
 
 
@@ -200,6 +201,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_crc_device": ([P, I, PP, SP, S, S, S, P, P, P, P], I),
         "hec_scrub_crc_mixed_workspace_size": ([P, S], S),
         "hec_scrub_crc_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
+        "hec_crc_concat": ([I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)], I),
+        "hec_composite_crc": ([I, P, S, S, S, S, S, ctypes.c_uint64, P, P, P], I),
+        "hec_composite_crc_workspace_size": ([S, S], S),
+        "hec_composite_crc_device": ([P, I, P, S, S, S, S, S, ctypes.c_uint64, P, P, P, P, S, P], I),
     }
     if hasattr(lib, "hec_tune_set"):  # the measurement build only (include/hdfs_ec_amd_exp.h)
         sig["hec_tune_set"] = ([I, I], I)
@@ -376,6 +381,41 @@ def scrub_verdict(ruled_out: int, bad_bytes: int, units: int):
 
 ALLOC_DEFAULT = 0
 ALLOC_CONTIGUOUS = 1
+
+
+def crc_concat(checksum_type: int, crc_a: int, crc_b: int, len_b: int) -> int:
+    """crc(A || B) from crc(A), crc(B) and |B| (hec_crc_concat)."""
+    out = ctypes.c_uint32()
+    _check(lib.hec_crc_concat(checksum_type, crc_a, crc_b, len_b, ctypes.byref(out)))
+    return out.value
+
+
+def composite_crc_workspace_size(n_units: int, stripes: int) -> int:
+    return lib.hec_composite_crc_workspace_size(n_units, stripes)
+
+
+def composite_crc(checksum_type: int, sums, n_units: int, data_units: int, cell_len: int, stripes: int,
+                  bytes_per_checksum: int = 512, data_len: int = 0, want=("cell", "unit", "group")):
+    """hec_composite_crc on the host: `sums` is the [stripes][n_units][nck]
+    big-endian chunk-sum array (bytes-like).  Returns (cell_crcs, unit_crcs,
+    group_crc): lists of ints ([stripes][n_units], [n_units]) and an int, None
+    for an output not in `want`."""
+    buf = (ctypes.c_uint8 * max(1, len(sums))).from_buffer_copy(bytes(sums) or b"\0")
+    cell = (ctypes.c_uint8 * max(1, 4 * stripes * n_units))() if "cell" in want else None
+    unit = (ctypes.c_uint8 * (4 * n_units))() if "unit" in want else None
+    group = (ctypes.c_uint8 * 4)() if "group" in want else None
+    _check(lib.hec_composite_crc(checksum_type, buf, n_units, data_units, cell_len, stripes, bytes_per_checksum,
+                                 data_len, cell, unit, group))
+
+    def words(b, count):
+        return [int.from_bytes(bytes(b[4 * i:4 * i + 4]), "big") for i in range(count)]
+
+    cells = None
+    if cell is not None:
+        flat = words(cell, stripes * n_units)
+        cells = [flat[s * n_units:(s + 1) * n_units] for s in range(stripes)]
+    return (cells, words(unit, n_units) if unit is not None else None,
+            words(group, 1)[0] if group is not None else None)
 
 
 class DeviceBuffer:
@@ -671,6 +711,20 @@ class Coder:
                                               stripes, bytes_per_checksum, ctypes.c_void_p(expected_ptr),
                                               ctypes.c_void_p(bad_ptr), ctypes.c_void_p(stream)))
 
+    def composite_crc_device(self, checksum_type: int, sums_ptr: int, n_units: int, data_units: int, cell_len: int,
+                             stripes: int, bytes_per_checksum: int, data_len: int = 0, cell_crcs_ptr: int = 0,
+                             unit_crcs_ptr: int = 0, group_crc_ptr: int = 0, workspace: int = 0,
+                             workspace_bytes: int = 0, stream: int = 0) -> None:
+        """hec_composite_crc_device: cell / unit / group CRCs (big-endian u32,
+        each optional: 0 = not computed) from the chunk sums at sums_ptr,
+        asynchronously on `stream`.  The workspace
+        (composite_crc_workspace_size(n_units, stripes) bytes) is needed for
+        the unit and group outputs."""
+        _check(self._lib.hec_composite_crc_device(self._h, checksum_type, sums_ptr, n_units, data_units, cell_len,
+                                                  stripes, bytes_per_checksum, data_len, cell_crcs_ptr or None,
+                                                  unit_crcs_ptr or None, group_crc_ptr or None, workspace or None,
+                                                  workspace_bytes, stream or None))
+
     def decode_verify_device(self, checksum_type: int, shard_ptrs, shard_strides, out_ptrs, out_strides, cell_len,
                              stripes, bytes_per_checksum, sums_ptr, bad_ptr, stream: int = 0) -> None:
         """Verified striped read (hec_decode_verify_device): raises
@@ -862,6 +916,36 @@ def checksum_batch(coder: Coder, cells, checksum_type: int = CHECKSUM_CRC32C, by
     ptrs, strides = stripe_layout_ptrs(cells, n)
     coder.checksum_device(checksum_type, ptrs, strides, cell, S, bytes_per_checksum, out.data_ptr(), s.cuda_stream)
     return out
+
+
+def composite_crc_batch(coder: Coder, sums, data_units: int, cell_len: int, checksum_type: int = CHECKSUM_CRC32C,
+                        bytes_per_checksum: int = 512, data_len: int = 0, want=("cell", "unit", "group"),
+                        stream=None, workspace=None):
+    """sums: uint8 cuda tensor [S, n, nchunks, 4] as checksum_batch returns ->
+    (cell_crcs [S, n, 4], unit_crcs [n, 4], group_crc [4]) uint8 tensors of
+    big-endian CRCs, None for an output not in `want`.  Asynchronous on the
+    stream; the workspace is allocated here unless one is passed."""
+    import torch
+    S, n = sums.shape[0], sums.shape[1]
+    assert sums.is_contiguous() and sums.shape[2] == (cell_len + bytes_per_checksum - 1) // bytes_per_checksum
+    s = stream if stream is not None else torch.cuda.current_stream(sums.device)
+
+    def out(*shape):
+        return torch.empty(shape, dtype=torch.uint8, device=sums.device)
+
+    cell = out(S, n, 4) if "cell" in want else None
+    unit = out(n, 4) if "unit" in want else None
+    group = out(4) if "group" in want else None
+    if workspace is None and (unit is not None or group is not None):
+        workspace = out(max(4, composite_crc_workspace_size(n, S)))
+    coder.composite_crc_device(checksum_type, sums.data_ptr(), n, data_units, cell_len, S, bytes_per_checksum, data_len,
+                               cell.data_ptr() if cell is not None else 0, unit.data_ptr() if unit is not None else 0,
+                               group.data_ptr() if group is not None else 0,
+                               workspace.data_ptr() if workspace is not None else 0,
+                               workspace.numel() if workspace is not None else 0, s.cuda_stream)
+    if workspace is not None:
+        workspace.record_stream(s)
+    return cell, unit, group
 
 
 def checksum_verify_batch(coder: Coder, cells, expected, checksum_type: int = CHECKSUM_CRC32C,

@@ -617,6 +617,62 @@ int hec_checksum_verify_device(hec_coder_t *coder, int checksum_type, const uint
                                size_t bytes_per_checksum, const uint8_t *d_expected, uint8_t *d_bad,
                                void *hip_stream);
 
+/* ---- Composite CRCs: cell, block and block-group sums from chunk sums ---- *
+ * HDFS reports no chunk sums outward: with COMPOSITE_CRC a DataNode answers
+ * OpBlockChecksum / OpBlockGroupChecksum with the CRC of a whole internal
+ * block (optionally one per cell, stripeLength = cellSize) and the client
+ * folds the cell CRCs of a block group, in file order, into the CRC of the
+ * logical bytes.  These calls fold the [stripe][n_units][nck] chunk sums the
+ * calls above leave behind, nck = ceil(cell_len / bytes_per_checksum); they
+ * never read a cell.
+ *
+ * hec_crc_concat: *out = crc(A || B) from crc_a = crc(A), crc_b = crc(B) and
+ * len_b = |B|, with crc(A || B) = L(crc(A) ^ xorout ^ init) ^ crc(B) where L
+ * appends len_b zero bytes to the register (a multiply by x^(8 len_b) mod P).
+ * HEC_CHECKSUM_CRC32C or HEC_CHECKSUM_CRC32; others -> HEC_ERR_INVALID_ARG.
+ *
+ * Geometry of the composite calls: the first data_units of the n_units units
+ * per stripe are data.  data_len is the logical length of the group: 0 means
+ * stripes * data_units * cell_len, otherwise (stripes-1) * data_units *
+ * cell_len < data_len <= stripes * data_units * cell_len and only the last
+ * stripe is short: with r bytes in it, data unit u holds min(cell_len,
+ * max(0, r - u * cell_len)) and every parity unit min(cell_len, r), the first
+ * cell's length.  Chunk c of a cell covers its bytes [c * bpc, min((c+1) *
+ * bpc, len)); slots past ceil(len / bpc) are never read.  Outputs, big-endian
+ * u32 like the sums, each optional (NULL = not computed, not written):
+ *   cell_crcs[stripe][n_units]  CRC of each cell (crc(empty) for length 0);
+ *   unit_crcs[n_units]          CRC of cells (0,u) || (1,u) || ...: internal block u;
+ *   group_crc[1]                CRC of the data cells in file order (stripe,
+ *                               then unit 0 .. data_units-1): the data_len logical bytes.
+ * Each output depends only on the slots of its own cells.
+ *
+ * hec_composite_crc runs on the host and needs no coder.  HEC_ERR_INVALID_ARG
+ * for NULL sums, cell_len == 0, bytes_per_checksum == 0, n_units not in
+ * 1..64, data_units not in 1..n_units, data_len out of range (with stripes ==
+ * 0 only 0 is in range), HEC_CHECKSUM_NULL or an unknown type.  HEC_OK,
+ * nothing written, for stripes == 0.
+ *
+ * hec_composite_crc_device does the same on the coder's device,
+ * asynchronously on hip_stream: it never synchronises, allocates or reads
+ * back, so it can be captured into a graph.  d_sums is only read; nothing but
+ * the requested outputs and the workspace is written.  d_workspace
+ * (hec_composite_crc_workspace_size(n_units, stripes) bytes, 4-byte aligned)
+ * is needed only when d_unit_crcs or d_group_crc is asked for, is untouched
+ * until the stream reaches the work, and must differ between calls in flight
+ * at once.  HEC_ERR_DEVICE on a host-only coder.  HEC_ERR_INVALID_ARG,
+ * nothing queued: the host call's cases, a NULL coder, d_sums or an output
+ * not 4-byte aligned, a needed workspace that is NULL, misaligned or too
+ * small.  HEC_OK, nothing queued: stripes == 0 or all three outputs NULL. */
+int hec_crc_concat(int checksum_type, uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *out);
+int hec_composite_crc(int checksum_type, const uint8_t *sums, size_t n_units, size_t data_units, size_t cell_len,
+                      size_t stripes, size_t bytes_per_checksum, uint64_t data_len, uint8_t *cell_crcs,
+                      uint8_t *unit_crcs, uint8_t *group_crc);
+size_t hec_composite_crc_workspace_size(size_t n_units, size_t stripes);
+int hec_composite_crc_device(hec_coder_t *coder, int checksum_type, const uint8_t *d_sums, size_t n_units,
+                             size_t data_units, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                             uint64_t data_len, uint8_t *d_cell_crcs, uint8_t *d_unit_crcs, uint8_t *d_group_crc,
+                             void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* The striped read of one batch of rows (block_reader.rs:480-525 feeding
  * EcSchema::ec_decode, ec/mod.rs:62-89) with every cell it consumes
  * checksum-verified.  d_shards[k+m] as hec_decode_device (NULL = shard not

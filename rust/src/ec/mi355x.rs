@@ -130,6 +130,15 @@ unsafe extern "C" {
                                   stripes: usize, bytes_per_checksum: usize, d_expected: *const u8,
                                   d_bad: *mut u8, d_results: *mut ScrubResult, d_workspace: *mut c_void,
                                   workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    fn hec_crc_concat(checksum_type: c_int, crc_a: u32, crc_b: u32, len_b: u64, out: *mut u32) -> c_int;
+    fn hec_composite_crc(checksum_type: c_int, sums: *const u8, n_units: usize, data_units: usize, cell_len: usize,
+                         stripes: usize, bytes_per_checksum: usize, data_len: u64, cell_crcs: *mut u8,
+                         unit_crcs: *mut u8, group_crc: *mut u8) -> c_int;
+    fn hec_composite_crc_workspace_size(n_units: usize, stripes: usize) -> usize;
+    fn hec_composite_crc_device(c: *mut HecCoder, checksum_type: c_int, d_sums: *const u8, n_units: usize,
+                                data_units: usize, cell_len: usize, stripes: usize, bytes_per_checksum: usize,
+                                data_len: u64, d_cell_crcs: *mut u8, d_unit_crcs: *mut u8, d_group_crc: *mut u8,
+                                d_workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
     fn hec_device_alloc(device: c_int, bytes: usize, flags: u32, out: *mut *mut c_void) -> c_int;
     fn hec_device_free(device: c_int, ptr: *mut c_void) -> c_int;
     fn hec_device_copy(device: c_int, dst: *mut c_void, src: *const c_void, bytes: usize) -> c_int;
@@ -497,6 +506,63 @@ impl GpuCoder {
             hec_scrub_crc_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
                                        present.as_ptr(), cell, present.len(), bytes_per_checksum, expected, bad,
                                        results, workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// `hec_crc_concat`: crc(A || B) from crc(A), crc(B) and |B|.
+    pub fn crc_concat(checksum_type: i32, crc_a: u32, crc_b: u32, len_b: u64) -> Result<u32> {
+        let mut out = 0u32;
+        check(unsafe { hec_crc_concat(checksum_type as c_int, crc_a, crc_b, len_b, &mut out) })?;
+        Ok(out)
+    }
+
+    /// `hec_composite_crc` on the host: the CRC of every cell (`[stripes][n_units]`),
+    /// of every internal block (`[n_units]`) and of the `data_len` logical
+    /// bytes, from the `[stripes][n_units][nck]` big-endian chunk sums.
+    /// `data_len == 0` means every stripe is full.
+    #[allow(clippy::too_many_arguments)]
+    pub fn composite_crc(checksum_type: i32, sums: &[u8], n_units: usize, data_units: usize, cell: usize,
+                         stripes: usize, bytes_per_checksum: usize, data_len: u64)
+                         -> Result<(Vec<u32>, Vec<u32>, u32)> {
+        assert!(cell > 0 && bytes_per_checksum > 0, "cell and bytes_per_checksum must be positive");
+        let nck = cell.div_ceil(bytes_per_checksum);
+        assert!(sums.len() >= 4 * stripes * n_units * nck, "one u32 per chunk slot");
+        let mut cells = vec![0u8; 4 * stripes * n_units];
+        let mut units = vec![0u8; 4 * n_units];
+        let mut group = [0u8; 4];
+        check(unsafe {
+            hec_composite_crc(checksum_type as c_int, sums.as_ptr(), n_units, data_units, cell, stripes,
+                              bytes_per_checksum, data_len, cells.as_mut_ptr(), units.as_mut_ptr(),
+                              group.as_mut_ptr())
+        })?;
+        let words = |b: &[u8]| b.chunks_exact(4).map(|w| u32::from_be_bytes([w[0], w[1], w[2], w[3]])).collect();
+        Ok((words(&cells), words(&units), u32::from_be_bytes(group)))
+    }
+
+    /// Device bytes `composite_crc_device` needs for its unit and group outputs.
+    pub fn composite_crc_workspace_size(n_units: usize, stripes: usize) -> usize {
+        unsafe { hec_composite_crc_workspace_size(n_units, stripes) }
+    }
+
+    /// `hec_composite_crc_device`: the same fold on this coder's device,
+    /// asynchronously on `stream`, over chunk sums already there (as the
+    /// verified calls leave them).  Each output is optional (null = not
+    /// computed); `workspace` is needed for `unit_crcs` and `group_crc`.
+    ///
+    /// # Safety
+    /// `sums` valid for `stripes * n_units * ceil(cell / bytes_per_checksum)`
+    /// u32, the outputs for `stripes * n_units`, `n_units` and one u32,
+    /// `workspace` for `workspace_bytes`, all on this device and 4-byte aligned.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn composite_crc_device(&self, checksum_type: i32, sums: *const u8, n_units: usize,
+                                       data_units: usize, cell: usize, stripes: usize, bytes_per_checksum: usize,
+                                       data_len: u64, cell_crcs: *mut u8, unit_crcs: *mut u8, group_crc: *mut u8,
+                                       workspace: *mut c_void, workspace_bytes: usize,
+                                       stream: *mut c_void) -> Result<()> {
+        check(unsafe {
+            hec_composite_crc_device(self.raw, checksum_type as c_int, sums, n_units, data_units, cell, stripes,
+                                     bytes_per_checksum, data_len, cell_crcs, unit_crcs, group_crc, workspace,
+                                     workspace_bytes, stream)
         })
     }
 
