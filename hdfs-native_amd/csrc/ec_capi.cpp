@@ -38,6 +38,7 @@
 #include "crc_compose.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
+#include "ec_reconstruct_sums.hpp"
 #include "ec_scrub_crc.hpp"
 #include "gf256.hpp"
 #include "host_gf.hpp"
@@ -2798,6 +2799,249 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
         for (const CrcGroupCall& call : calls) {
             rc = recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
                                      bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return HEC_OK;
+    });
+}
+
+// ---- checksum-only reconstruction ---------------------------------------------
+// hec_reconstruct_sums_device*: the chunk sums of lost units from the
+// survivors, nothing rebuilt written (ec_reconstruct_sums.hip).  Read-only
+// over the cells; only the targets' live sums words and d_bad are written.
+
+}  // extern "C"
+
+namespace {
+
+// Byte lengths of a group's units in its short last stripe; null = full cells.
+struct SumsLens {
+    const uint64_t* len = nullptr;  // [k + m]
+    size_t stripe0 = 0;             // the stripe the lengths describe (the launch is that one stripe)
+};
+
+int recon_sums_check(const hec_coder* c, int checksum_type, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                     const uint8_t* d_bad, const uint8_t* d_sums, int* kind) {
+    if (!c || cell_len == 0) return HEC_ERR_INVALID_ARG;
+    *kind = crc_kind(checksum_type);  // HEC_CHECKSUM_NULL: nothing to compute
+    if (*kind < 0 || bpc == 0 || !d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
+        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// The fused launch of one group of full stripes.  0 ok, -1 refused by the
+// launcher (nothing launched), else HEC_*.
+int recon_sums_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                     const size_t* shard_strides, size_t cell_len, const uint8_t* d_expected, uint8_t* d_bad,
+                     uint8_t* d_sums, hipStream_t stream) {
+    const size_t k = c->k;
+    const DecodePlan& p = *g.rp->plan;
+    hec::MatmulArgs a;
+    std::memset(&a, 0, sizeof(a));
+    hec::ReconCrcArgs cs;
+    std::memset(&cs, 0, sizeof(cs));
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = p.rec_survivors[r];
+        a.in[r] = d_shards[u];
+        a.in_stride[r] = shard_strides[u];
+        cs.shard_id[r] = uint8_t(u);
+    }
+    for (size_t j = 0; j < g.rp->rows.size(); j++) {
+        const size_t row = g.rp->rows[j];
+        cs.shard_id[k + j] = uint8_t(p.lost[row]);
+        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+    }
+    a.k = int32_t(k);
+    a.r = int32_t(g.rp->rows.size());
+    a.cell_len = cell_len;
+    a.stripes = g.stripes;
+    cs.sums = d_sums;
+    cs.expected = d_expected;
+    cs.bad = d_bad;
+    cs.n_total = uint32_t(c->k + c->m);
+    cs.kind = kind;
+    cs.stripe_list = g.d_list;
+    const int rc = hec::launch_reconstruct_sums(a, cs, c->device, stream);
+    if (rc <= 0) return rc;
+    return to_status(rc);
+}
+
+// The generic route of one group: gf_reconstruct_sums_bytes over the group's
+// rows, four per launch.  Full cells (lens.len == nullptr): the survivors are
+// verified by a checksum launch first.  A short last stripe: that one stripe,
+// every unit at its own length, the survivors verified by the same kernel.
+int recon_sums_generic(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                       const size_t* shard_strides, size_t cell_len, size_t bpc, const SumsLens& lens,
+                       const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
+    const size_t k = c->k, n = c->k + c->m;
+    const DecodePlan& p = *g.rp->plan;
+    if (d_expected && !lens.len) {
+        const uint8_t* bases[HEC_MAX_DATA_UNITS];
+        size_t strides[HEC_MAX_DATA_UNITS];
+        uint8_t sid[HEC_MAX_DATA_UNITS];
+        for (size_t r = 0; r < k; r++) {
+            const size_t u = p.rec_survivors[r];
+            bases[r] = d_shards[u];
+            strides[r] = shard_strides[u];
+            sid[r] = uint8_t(u);
+        }
+        const int rc = checksum_launch(c, kind, bases, strides, sid, k, n, cell_len, g.stripes, bpc, nullptr,
+                                       d_expected, d_bad, stream, g.d_list);
+        if (rc != HEC_OK) return rc;
+    }
+    hec::ReconSumsArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = p.rec_survivors[r];
+        a.in[r] = d_shards[u];
+        a.in_stride[r] = shard_strides[u];
+        a.in_len[r] = lens.len ? lens.len[u] : cell_len;
+        a.in_id[r] = uint8_t(u);
+    }
+    a.k = int32_t(k);
+    a.sums = d_sums;
+    a.n_total = uint32_t(n);
+    a.kind = kind;
+    a.stripe_list = g.d_list;
+    a.stripe0 = lens.stripe0;
+    a.stripes = g.stripes;
+    a.bytes_per_checksum = bpc;
+    a.nck = cell_len / bpc + (cell_len % bpc != 0);
+    if (lens.len) {  // the first launch also verifies
+        a.expected = d_expected;
+        a.bad = d_bad;
+    }
+    for (size_t j0 = 0; j0 < g.rp->rows.size(); j0 += size_t(hec::kMaxR)) {
+        const size_t rn = std::min(size_t(hec::kMaxR), g.rp->rows.size() - j0);
+        std::memset(a.coef, 0, sizeof(a.coef));
+        for (size_t j = 0; j < rn; j++) {
+            const size_t row = g.rp->rows[j0 + j], u = p.lost[row];
+            a.out_id[j] = uint8_t(u);
+            a.out_len[j] = lens.len ? lens.len[u] : cell_len;
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+        }
+        a.r = int32_t(rn);
+        const int rc = hec::launch_reconstruct_sums_bytes(a, c->device, stream);
+        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+        a.expected = nullptr;
+        a.bad = nullptr;
+    }
+    return HEC_OK;
+}
+
+// Full stripes of one group: the fused kernel where it takes the shape, else
+// the generic route.
+int recon_sums_group(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
+                     const size_t* shard_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                     uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
+    if (g.stripes == 0) return HEC_OK;
+    bool fused = recon_crc_shape(c, cell_len, bpc) && g.rp->rows.size() <= size_t(hec::kMaxR);
+    if (fused) {
+        uint64_t survivors = 0;
+        for (size_t r = 0; r < c->k; r++) survivors |= uint64_t(1) << g.rp->plan->rec_survivors[r];
+        fused = aligned16(d_shards, shard_strides, survivors);
+    }
+    if (fused) {
+        const int rc = recon_sums_fused(c, kind, g, d_shards, shard_strides, cell_len, d_expected, d_bad, d_sums, stream);
+        if (rc != -1) return rc;  // -1: refused, nothing launched
+    }
+    return recon_sums_generic(c, kind, g, d_shards, shard_strides, cell_len, bpc, SumsLens{}, d_expected, d_bad,
+                              d_sums, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_reconstruct_sums_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                const size_t* shard_strides, const uint8_t* want, size_t cell_len, size_t stripes,
+                                size_t bytes_per_checksum, uint64_t data_len, const uint8_t* d_expected,
+                                uint8_t* d_bad, uint8_t* d_sums, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_sums_device");
+    int kind;
+    const int chk = recon_sums_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    if (chk != HEC_OK) return chk;
+    hec::crc::Geometry geo;
+    if (!d_shards || !shard_strides ||
+        !hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
+        return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        const size_t n = c->k + c->m;
+        uint64_t mask = 0, want_mask = 0;
+        for (size_t i = 0; i < n; i++)
+            if (d_shards[i]) mask |= uint64_t(1) << i;
+        for (size_t i = 0; want && i < n; i++)
+            if (want[i]) want_mask |= uint64_t(1) << i;
+        if (want_mask & mask) return HEC_ERR_INVALID_ARG;  // a present unit is not rebuilt
+        RowPlan rp;
+        rp.plan = plan_of_mask(c, mask);
+        if (stripes != 0) rp.rows = target_rows(*rp.plan, want != nullptr, want_mask);
+        if (rp.rows.empty()) return HEC_OK;
+        if (rp.plan->rec_status != HEC_OK) return rp.plan->rec_status;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        // only the last stripe can be short: the others as one group of full cells
+        const bool short_last = geo.last_len < uint64_t(c->k) * cell_len;
+        const CrcGroupCall full{&rp, short_last ? stripes - 1 : stripes, nullptr};
+        int rc = recon_sums_group(c, kind, full, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
+                                  d_bad, d_sums, stream);
+        if (rc != HEC_OK || !short_last) return rc;
+        const CrcGroupCall last{&rp, 1, nullptr};
+        return recon_sums_generic(c, kind, last, d_shards, shard_strides, cell_len, bytes_per_checksum,
+                                  SumsLens{geo.len_last, stripes - 1}, d_expected, d_bad, d_sums, stream);
+    });
+}
+
+int hec_reconstruct_sums_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                      const size_t* shard_strides, const uint64_t* present, const uint64_t* want,
+                                      size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                      const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, void* d_workspace,
+                                      size_t workspace_bytes, void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_sums_device_mixed");
+    int kind;
+    const int chk = recon_sums_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    if (chk != HEC_OK) return chk;
+    if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    // a unit without storage (the dead node's) is present in no stripe
+    uint64_t ever_present = 0;
+    for (size_t s = 0; s < stripes; s++) ever_present |= present[s];
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i] && ((ever_present >> i) & 1)) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        // the distinct (present, want) pairs with a target, each with its plan
+        // and the list of its stripes (host); fail before launching anything
+        Batch batch;
+        int rc = group_stripes(
+            c, present, stripes, kNoPlanId, [&](size_t s, uint64_t mask) { return want ? want[s] : ~mask; },
+            [&](uint64_t mask, uint64_t wmask, RowPlan* rp) { return reconstruct_rows(c, mask, wmask, rp); }, &batch);
+        if (rc != HEC_OK) return rc;
+        if (batch.plans.empty()) return HEC_OK;
+        // the lists where hec_reconstruct_crc_device_mixed keeps them: one
+        // workspace, one size function, one rule for both calls
+        const size_t lists_pos = align_up(recon_workspace(c->k, c->m, stripes));
+        std::vector<uint32_t> flat;
+        std::vector<size_t> off;
+        stripe_lists(batch, &flat, &off);
+        const size_t lists_bytes = flat.size() * sizeof(uint32_t);
+        if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) || workspace_bytes < lists_pos + lists_bytes)
+            return HEC_ERR_INVALID_ARG;
+        uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+                           [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
+        if (rc != HEC_OK) return rc;
+        // one launch per pair (more where a pair has over four rows or runs the generic route)
+        for (size_t gi = 0; gi < batch.plans.size(); gi++) {
+            const CrcGroupCall call{&batch.plans[gi], off[gi + 1] - off[gi],
+                                    reinterpret_cast<const uint32_t*>(d_lists) + off[gi]};
+            rc = recon_sums_group(c, kind, call, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
+                                  d_bad, d_sums, stream);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;

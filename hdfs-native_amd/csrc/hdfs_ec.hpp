@@ -353,6 +353,48 @@ class Coder {
                                                d_workspace, workspace_bytes, hip_stream));
     }
 
+    // Checksum-only reconstruction (hec_reconstruct_sums_device): the chunk
+    // sums of the lost units (d_units[i] == nullptr, or those in want) from
+    // the survivors, written to their slots of d_sums; no cell byte is
+    // written.  data_len as for hec_composite_crc (0 = every stripe full);
+    // d_expected / d_bad as for reconstruct_crc_device.
+    void reconstruct_sums_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                 const std::vector<size_t>& strides, const std::vector<size_t>* want, size_t cell_len,
+                                 size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                                 const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums,
+                                 void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units)
+            throw std::invalid_argument("reconstruct_sums_device: need data_units + parity_units slots");
+        std::vector<uint8_t> want_flags(units, 0);
+        if (want)
+            for (size_t t : *want) {
+                if (t >= units) throw std::invalid_argument("reconstruct_sums_device: want index out of range");
+                want_flags[t] = 1;
+            }
+        check(hec_reconstruct_sums_device(h_.get(), checksum_type, d_units.data(), strides.data(),
+                                          want ? want_flags.data() : nullptr, cell_len, stripes, bytes_per_checksum,
+                                          data_len, d_expected, d_bad, d_sums, hip_stream));
+    }
+    // One pattern per stripe, full stripes only
+    // (hec_reconstruct_sums_device_mixed); d_units[i] may be nullptr for a unit
+    // no stripe has present; d_workspace as for reconstruct_crc_device_mixed.
+    void reconstruct_sums_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                       const std::vector<size_t>& strides, const std::vector<uint64_t>& present,
+                                       const std::vector<uint64_t>* want, size_t cell_len, size_t bytes_per_checksum,
+                                       const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, void* d_workspace,
+                                       size_t workspace_bytes, void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units)
+            throw std::invalid_argument("reconstruct_sums_device_mixed: need data_units + parity_units slots");
+        if (want && want->size() != present.size())
+            throw std::invalid_argument("reconstruct_sums_device_mixed: one want mask per stripe");
+        check(hec_reconstruct_sums_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(),
+                                                present.data(), want ? want->data() : nullptr, cell_len,
+                                                present.size(), bytes_per_checksum, d_expected, d_bad, d_sums,
+                                                d_workspace, workspace_bytes, hip_stream));
+    }
+
    private:
     ScrubResult make_result(const hec_scrub_result_t& r) const {
         ScrubResult s;

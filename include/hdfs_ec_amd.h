@@ -362,6 +362,68 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t *coder, int checksum_type,
                                      const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums,
                                      void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* Checksum-only reconstruction: the chunk sums of lost units, computed from
+ * the survivors, with nothing rebuilt written to memory -- what
+ * StripedBlockChecksumReconstructor does for the block (group) checksum of a
+ * degraded group (HDFS-9833; COMPOSITE_CRC: HDFS-13056).  The two calls above
+ * with d_out / out_strides removed: survivors (the first k present units),
+ * plans, want, the layout and alignment of d_sums / d_expected / d_bad,
+ * d_expected == d_sums, flags only ever set, asynchronous (no
+ * synchronisation, no allocation, no read-back), HEC_ERR_NOT_ENOUGH_SHARDS
+ * with nothing queued and HEC_ERR_DEVICE on a host-only coder are theirs.
+ * What differs:
+ *   Read-only over the cells: no byte of any unit slot is written, lost slots
+ *     included.  Only the sums words of the target units' live chunks are
+ *     written, plus d_bad on a mismatch.
+ *   HEC_CHECKSUM_NULL is HEC_ERR_INVALID_ARG (nothing to compute, as for
+ *     hec_checksum_device).
+ *   data_len (uniform form) has the meaning and the range check of
+ *     hec_composite_crc: 0 = every stripe full; otherwise the last stripe
+ *     holds r = data_len - (stripes-1)*k*cell_len logical bytes, n0 =
+ *     min(cell_len, r), and unit u has len(u) bytes there (data unit u: what
+ *     is left of r past u*cell_len, at most cell_len; parity: n0).  In that
+ *     stripe each present unit's slot holds its len(u) bytes followed by zeros
+ *     up to n0 (CellReader::next_cell's padding); nothing at or past n0 is
+ *     read from any slot.  A rebuilt unit t is computed over [0, n0); its sums
+ *     are written for chunks c < ceil(len(t) / bytes_per_checksum), the last
+ *     one over [c*bpc, len(t)); the slots past that -- all of them when len(t)
+ *     == 0 -- are not written.  With d_expected a survivor is verified over
+ *     its own len(u) bytes; a present unit of length 0 contributes zeros and
+ *     none of its sums words is read.  These are the sums hec_composite_crc*
+ *     expects, so a degraded group's block and group CRCs are this call and
+ *     hec_composite_crc_device with the same data_len on one stream.
+ *   Mixed form: full stripes only (a batch spans groups).  d_shards[i] may be
+ *     NULL if no stripe's `present` has bit i -- the dead node's unit, for
+ *     which the caller has no storage; a NULL slot some stripe has present is
+ *     HEC_ERR_INVALID_ARG with nothing queued.  The workspace is the one of
+ *     hec_reconstruct_crc_device_mixed (hec_reconstruct_crc_mixed_workspace_size,
+ *     same rules); it holds the stripe lists.  One launch per distinct
+ *     (present, want) pair; stripes without a target are skipped.
+ * HEC_ERR_INVALID_ARG, nothing queued: NULL coder, HEC_CHECKSUM_NULL or an
+ * unknown type, cell_len == 0, bytes_per_checksum == 0, NULL or misaligned
+ * d_sums, d_expected without d_bad, data_len out of range, a workspace that is
+ * too small, NULL or misaligned.  HEC_OK, nothing queued: stripes == 0 or no
+ * target anywhere.
+ * Full stripes run the kernel of hec_reconstruct_crc_device without its
+ * output stores (reads k cells, writes the sums) for k in {2,3,6,10}, at most
+ * 4 target rows per pattern, bytes_per_checksum == 512 and 16-B aligned
+ * survivor bases, strides and cell_len.  Every other shape, and the short last
+ * stripe, runs a byte-wise kernel (one lane per stripe, target and chunk)
+ * behind a verify pass over the survivors: the same results.  The uniform
+ * form queues kernels only and can be captured into a graph. */
+int hec_reconstruct_sums_device(hec_coder_t *coder, int checksum_type,
+                                const uint8_t *const *d_shards, const size_t *shard_strides,
+                                const uint8_t *want, size_t cell_len, size_t stripes,
+                                size_t bytes_per_checksum, uint64_t data_len,
+                                const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums, void *hip_stream);
+
+int hec_reconstruct_sums_device_mixed(hec_coder_t *coder, int checksum_type,
+                                      const uint8_t *const *d_shards, const size_t *shard_strides,
+                                      const uint64_t *present, const uint64_t *want,
+                                      size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                      const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums,
+                                      void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ---- Scrub: verify a stripe's parity and locate a corrupt unit ----------- *
  * What a block scanner or a repair worker asks before and after it rebuilds
  * (`hdfs debug verifyEC`; dfs.datanode.ec.reconstruct.validation, HDFS-15759):

@@ -112,6 +112,16 @@ unsafe extern "C" {
                                         d_expected: *const u8, d_bad: *mut u8, d_sums: *mut u8,
                                         d_workspace: *mut c_void, workspace_bytes: usize,
                                         stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_sums_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                   shard_strides: *const usize, want: *const u8, cell_len: usize, stripes: usize,
+                                   bytes_per_checksum: usize, data_len: u64, d_expected: *const u8,
+                                   d_bad: *mut u8, d_sums: *mut u8, stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_sums_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                         shard_strides: *const usize, present: *const u64, want: *const u64,
+                                         cell_len: usize, stripes: usize, bytes_per_checksum: usize,
+                                         d_expected: *const u8, d_bad: *mut u8, d_sums: *mut u8,
+                                         d_workspace: *mut c_void, workspace_bytes: usize,
+                                         stream: *mut c_void) -> c_int;
     fn hec_scrub_verdict(ruled_out: u64, bad_bytes: u64, units: usize, unit: *mut c_int) -> c_int;
     fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
     fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
@@ -404,6 +414,60 @@ impl GpuCoder {
                                              present.as_ptr(), want.map_or(std::ptr::null(), |w| w.as_ptr()), cell,
                                              present.len(), bytes_per_checksum, expected, bad, sums, workspace,
                                              workspace_bytes, stream)
+        })
+    }
+
+    /// The chunk sums of the lost units of a block group, reconstructed from
+    /// the survivors, with nothing rebuilt written to memory
+    /// (`hec_reconstruct_sums_device`): what a degraded group's block (group)
+    /// checksum needs.  `shards`, `want`, `expected`, `bad` and `sums` as for
+    /// `reconstruct_crc_device`, but the cells are only read.  `data_len` as
+    /// for `hec_composite_crc`: 0 = every stripe full, otherwise the last
+    /// stripe is short and every sum covers the unit's true bytes, so
+    /// `hec_composite_crc_device` with the same `data_len` on the same stream
+    /// turns `sums` into the block and group CRCs.  `checksum_type` is CRC32C
+    /// or CRC32.
+    ///
+    /// # Safety
+    /// As `reconstruct_crc_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_sums_device(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                          want: Option<&[usize]>, cell: usize, stripes: usize,
+                                          bytes_per_checksum: usize, data_len: u64, expected: *const u8,
+                                          bad: *mut u8, sums: *mut u8, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        let flags = want.map(|w| want_flags(n, w));
+        check(unsafe {
+            hec_reconstruct_sums_device(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
+                                        flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()), cell, stripes,
+                                        bytes_per_checksum, data_len, expected, bad, sums, stream)
+        })
+    }
+
+    /// `reconstruct_sums_device` with one pattern per stripe, full stripes
+    /// only (`hec_reconstruct_sums_device_mixed`).  `shards[i]` may be null for
+    /// a unit no stripe has present: the dead node's.  `workspace` is device
+    /// memory of `reconstruct_crc_mixed_workspace_size(stripes)` bytes,
+    /// untouched until `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `reconstruct_crc_device_mixed`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_sums_device_mixed(&self, checksum_type: i32, shards: &[*const u8],
+                                                shard_strides: &[usize], present: &[u64], want: Option<&[u64]>,
+                                                cell: usize, bytes_per_checksum: usize, expected: *const u8,
+                                                bad: *mut u8, sums: *mut u8, workspace: *mut c_void,
+                                                workspace_bytes: usize, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(want.map_or(true, |w| w.len() == present.len()), "one want mask per stripe");
+        check(unsafe {
+            hec_reconstruct_sums_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(),
+                                              shard_strides.as_ptr(), present.as_ptr(),
+                                              want.map_or(std::ptr::null(), |w| w.as_ptr()), cell, present.len(),
+                                              bytes_per_checksum, expected, bad, sums, workspace, workspace_bytes,
+                                              stream)
         })
     }
 
