@@ -38,6 +38,7 @@
 #include "crc_compose.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
+#include "ec_reconstruct_rows.hpp"
 #include "ec_reconstruct_sums.hpp"
 #include "ec_scrub_crc.hpp"
 #include "gf256.hpp"
@@ -1238,6 +1239,84 @@ void stripe_lists(const Batch& b, std::vector<uint32_t>* flat, std::vector<size_
     std::vector<size_t> at(off->begin(), off->end() - 1);
     for (size_t s = 0; s < b.stripe_plan.size(); s++)
         if (b.stripe_plan[s] != kNoPlanId) (*flat)[at[b.stripe_plan[s]]++] = uint32_t(s);
+}
+
+// hec_reconstruct_crc_rows_device_mixed: stripe s holds stripe_bytes[s]
+// logical bytes; 0 and k * cell_len both say "full".
+inline bool rows_short(uint64_t bytes, size_t k, size_t cell_len) {
+    return bytes != 0 && bytes != uint64_t(k) * cell_len;
+}
+
+// stripe_lists with every plan's stripes split in two: its full stripes and
+// its short ones (both ascending, flat in plan order), and the short stripes'
+// logical bytes beside their list entries.  stripe_bytes = null: all full.
+struct RowsLists {
+    std::vector<uint32_t> full, shrt;
+    std::vector<size_t> full_off, short_off;  // plan p's: [off[p], off[p + 1])
+    std::vector<uint64_t> short_bytes;        // of stripe shrt[i]
+};
+
+void rows_lists(const Batch& b, const uint64_t* stripe_bytes, size_t k, size_t cell_len, RowsLists* l) {
+    const size_t plans = b.plans.size();
+    l->full_off.assign(plans + 1, 0);
+    l->short_off.assign(plans + 1, 0);
+    auto is_short = [&](size_t s) { return stripe_bytes && rows_short(stripe_bytes[s], k, cell_len); };
+    for (size_t s = 0; s < b.stripe_plan.size(); s++)
+        if (b.stripe_plan[s] != kNoPlanId) (is_short(s) ? l->short_off : l->full_off)[b.stripe_plan[s] + 1]++;
+    for (size_t p = 0; p < plans; p++) {
+        l->full_off[p + 1] += l->full_off[p];
+        l->short_off[p + 1] += l->short_off[p];
+    }
+    l->full.resize(l->full_off.back());
+    l->shrt.resize(l->short_off.back());
+    l->short_bytes.resize(l->short_off.back());
+    std::vector<size_t> fat(l->full_off.begin(), l->full_off.end() - 1), sat(l->short_off.begin(), l->short_off.end() - 1);
+    for (size_t s = 0; s < b.stripe_plan.size(); s++) {
+        const uint32_t id = b.stripe_plan[s];
+        if (id == kNoPlanId) continue;
+        if (is_short(s)) {
+            l->short_bytes[sat[id]] = stripe_bytes[s];
+            l->shrt[sat[id]++] = uint32_t(s);
+        } else {
+            l->full[fat[id]++] = uint32_t(s);
+        }
+    }
+}
+
+// Where the lists sit in the workspace: the full stripes' where
+// hec_reconstruct_crc_device_mixed keeps its lists, then, behind that call's
+// whole workspace, [short lists: u32][pad to kAlign][their bytes: u64].
+// image_bytes = what one upload to full_pos carries (without a short stripe:
+// the full lists and nothing else, as hec_reconstruct_crc_device_mixed).
+struct RowsLayout {
+    size_t full_pos, short_pos, bytes_pos, need, image_bytes;
+};
+
+RowsLayout rows_layout(size_t k, size_t m, size_t stripes, size_t n_full, size_t n_short) {
+    RowsLayout w;
+    w.full_pos = align_up(recon_workspace(k, m, stripes));
+    w.short_pos = align_up(recon_crc_workspace(k, m, stripes));
+    w.bytes_pos = w.short_pos + align_up(n_short * sizeof(uint32_t));
+    w.need = n_short ? w.bytes_pos + n_short * sizeof(uint64_t) : w.full_pos + n_full * sizeof(uint32_t);
+    w.image_bytes = w.need - w.full_pos;
+    return w;
+}
+
+// The worst batch of `stripes`: every stripe short.
+size_t recon_rows_workspace(size_t k, size_t m, size_t stripes) {
+    return rows_layout(k, m, stripes, 0, stripes).bytes_pos + stripes * sizeof(uint64_t);
+}
+
+// Writes every byte of the image (lists, lengths, zeroes in the pads); host =
+// the image's first byte, which goes to workspace + w.full_pos.
+void write_rows_image(uint8_t* host, const RowsLists& l, const RowsLayout& w) {
+    const size_t full_bytes = l.full.size() * sizeof(uint32_t), short_bytes = l.shrt.size() * sizeof(uint32_t);
+    if (full_bytes) std::memcpy(host, l.full.data(), full_bytes);
+    if (l.shrt.empty()) return;
+    std::memset(host + full_bytes, 0, w.short_pos - w.full_pos - full_bytes);
+    std::memcpy(host + (w.short_pos - w.full_pos), l.shrt.data(), short_bytes);
+    std::memset(host + (w.short_pos - w.full_pos) + short_bytes, 0, w.bytes_pos - w.short_pos - short_bytes);
+    std::memcpy(host + (w.bytes_pos - w.full_pos), l.short_bytes.data(), l.short_bytes.size() * sizeof(uint64_t));
 }
 
 // The workspace image of a batch: the layout, and each plan's offset in the blob.
@@ -3042,6 +3121,265 @@ int hec_reconstruct_sums_device_mixed(hec_coder_t* c, int checksum_type, const u
                                     reinterpret_cast<const uint32_t*>(d_lists) + off[gi]};
             rc = recon_sums_group(c, kind, call, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
                                   d_bad, d_sums, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return HEC_OK;
+    });
+}
+
+// ---- verified reconstruction of short stripes ---------------------------------
+// hec_reconstruct_crc_rows_device*: hec_reconstruct_crc_device* for stripes
+// that hold fewer than k * cell_len logical bytes (ec_reconstruct_rows.hip).
+// Full stripes go through the launches of hec_reconstruct_crc_device*.
+
+}  // extern "C"
+
+namespace {
+
+// What needs no device and no buffer: the coder, the checksum (HEC_CHECKSUM_NULL
+// has no call of this kind) and the sizes.
+int recon_rows_check(const hec_coder* c, int checksum_type, size_t cell_len, size_t bpc, int* kind) {
+    if (!c || cell_len == 0 || bpc == 0) return HEC_ERR_INVALID_ARG;
+    *kind = crc_kind(checksum_type);
+    if (*kind < 0 || cell_len > UINT64_MAX / c->k) return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+int recon_rows_buffers_check(const uint8_t* d_expected, const uint8_t* d_bad, const uint8_t* d_sums) {
+    if (!d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
+        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// The short stripes of one group (g.stripes of them, g.d_list or lens.stripe0
+// on): gf_reconstruct_crc_rows where `fused` and the launcher takes it, else
+// gf_reconstruct_rows_bytes over the group's rows, four per launch, the first
+// launch verifying the survivors.
+int recon_rows_short(hec_coder* c, int kind, const CrcGroupCall& g, const hec::ReconRowsLens& lens, bool fused,
+                     const uint8_t* const* d_shards, const size_t* shard_strides, uint8_t* const* d_out,
+                     const size_t* out_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected, uint8_t* d_bad,
+                     uint8_t* d_sums, hipStream_t stream) {
+    if (g.stripes == 0) return HEC_OK;
+    const size_t k = c->k, n = c->k + c->m;
+    const DecodePlan& p = *g.rp->plan;
+    if (fused) {
+        hec::MatmulArgs a;
+        std::memset(&a, 0, sizeof(a));
+        hec::ReconCrcArgs cs;
+        std::memset(&cs, 0, sizeof(cs));
+        for (size_t r = 0; r < k; r++) {
+            const size_t u = p.rec_survivors[r];
+            a.in[r] = d_shards[u];
+            a.in_stride[r] = shard_strides[u];
+            cs.shard_id[r] = uint8_t(u);
+        }
+        for (size_t j = 0; j < g.rp->rows.size(); j++) {
+            const size_t row = g.rp->rows[j], u = p.lost[row];
+            a.out[j] = d_out[u];
+            a.out_stride[j] = out_strides[u];
+            cs.shard_id[k + j] = uint8_t(u);
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+        }
+        a.k = int32_t(k);
+        a.r = int32_t(g.rp->rows.size());
+        a.cell_len = cell_len;
+        a.stripes = g.stripes;
+        cs.sums = d_sums;
+        cs.expected = d_expected;
+        cs.bad = d_bad;
+        cs.n_total = uint32_t(n);
+        cs.kind = kind;
+        cs.stripe_list = g.d_list;
+        const int rc = hec::launch_reconstruct_crc_rows(a, cs, lens, c->device, stream);
+        if (rc == 0) return HEC_OK;
+        if (rc > 0) return to_status(rc);
+        // -1: refused, nothing launched
+    }
+    hec::ReconRowsBytesArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t r = 0; r < k; r++) {
+        const size_t u = p.rec_survivors[r];
+        a.in[r] = d_shards[u];
+        a.in_stride[r] = shard_strides[u];
+        a.in_id[r] = uint8_t(u);
+    }
+    a.k = int32_t(k);
+    a.data_units = uint32_t(k);
+    a.n_total = uint32_t(n);
+    a.sums = d_sums;
+    a.expected = d_expected;
+    a.bad = d_bad;
+    a.kind = kind;
+    a.stripe_list = g.d_list;
+    a.stripes = g.stripes;
+    a.lens = lens;
+    a.cell_len = cell_len;
+    a.bytes_per_checksum = bpc;
+    for (size_t j0 = 0; j0 < g.rp->rows.size(); j0 += size_t(hec::kMaxR)) {
+        const size_t rn = std::min(size_t(hec::kMaxR), g.rp->rows.size() - j0);
+        std::memset(a.coef, 0, sizeof(a.coef));
+        for (size_t j = 0; j < rn; j++) {
+            const size_t row = g.rp->rows[j0 + j], u = p.lost[row];
+            a.out[j] = d_out[u];
+            a.out_stride[j] = out_strides[u];
+            a.out_id[j] = uint8_t(u);
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+        }
+        a.r = int32_t(rn);
+        const int rc = hec::launch_reconstruct_rows_bytes(a, c->device, stream);
+        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+        a.expected = nullptr;  // the survivors are verified once
+        a.bad = nullptr;
+    }
+    return HEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_reconstruct_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                    const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
+                                    const uint8_t* want, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                    uint64_t data_len, const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums,
+                                    void* hip_stream) {
+    int kind;
+    const int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    hec::crc::Geometry geo;
+    if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
+        return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_rows_device");
+    if (recon_rows_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    // every stripe full: the existing call, launch for launch
+    if (stripes == 0 || geo.last_len == uint64_t(c->k) * cell_len)
+        return hec_reconstruct_crc_device(c, checksum_type, d_shards, shard_strides, d_out, out_strides, want, cell_len,
+                                          stripes, bytes_per_checksum, d_expected, d_bad, d_sums, hip_stream);
+    if (!d_shards || !shard_strides || stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        RowPlan rp;
+        const int prc = resolve_reconstruct(c, d_shards, want, d_out, d_out && out_strides, false, &rp);
+        if (prc != HEC_OK || rp.rows.empty()) return prc;
+        // one launch over the stripes - 1 full stripes, one over the last
+        if (stripes > 1) {
+            const int rc = hec_reconstruct_crc_device(c, checksum_type, d_shards, shard_strides, d_out, out_strides,
+                                                      want, cell_len, stripes - 1, bytes_per_checksum, d_expected,
+                                                      d_bad, d_sums, hip_stream);
+            if (rc != HEC_OK) return rc;
+        }
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const CrcGroupCall last{&rp, 1, nullptr};
+        const bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum) &&
+                           recon_crc_group_aligned(c, last, d_shards, shard_strides, d_out, out_strides);
+        return recon_rows_short(c, kind, last, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused, d_shards,
+                                shard_strides, d_out, out_strides, cell_len, bytes_per_checksum, d_expected, d_bad,
+                                d_sums, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+size_t hec_reconstruct_crc_rows_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return recon_rows_workspace(c->k, c->m, stripes);
+}
+
+int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                          const size_t* shard_strides, uint8_t* const* d_out,
+                                          const size_t* out_strides, const uint64_t* present, const uint64_t* want,
+                                          const uint64_t* stripe_bytes, size_t cell_len, size_t stripes,
+                                          size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                          uint8_t* d_sums, void* d_workspace, size_t workspace_bytes,
+                                          void* hip_stream) {
+    int kind;
+    const int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    for (size_t s = 0; stripe_bytes && s < stripes; s++)
+        if (stripe_bytes[s] > uint64_t(c->k) * cell_len) return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_rows_device_mixed");
+    if (recon_rows_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;  // every unit needs storage (present in some stripe)
+    return guarded([&]() -> int {
+        // 1. the distinct (present, want) pairs with a target and their plans
+        // (host); fail before anything is queued
+        Batch batch;
+        int rc = group_stripes(
+            c, present, stripes, kNoPlanId, [&](size_t s, uint64_t mask) { return want ? want[s] : ~mask; },
+            [&](uint64_t mask, uint64_t wmask, RowPlan* rp) { return reconstruct_rows(c, mask, wmask, rp); }, &batch);
+        if (rc != HEC_OK) return rc;
+        if (batch.plans.empty()) return HEC_OK;
+        if (!d_out || !out_strides || any_null(d_out, batch.target_units)) return HEC_ERR_INVALID_ARG;
+        // 2. every pair's full stripes and short stripes, the short ones' bytes
+        RowsLists lists;
+        rows_lists(batch, stripe_bytes, c->k, cell_len, &lists);
+        const RowsLayout w = rows_layout(c->k, c->m, stripes, lists.full.size(), lists.shrt.size());
+        if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 7u) || workspace_bytes < w.need)
+            return HEC_ERR_INVALID_ARG;
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        const uint32_t* d_full = reinterpret_cast<const uint32_t*>(ws + w.full_pos);
+        const uint32_t* d_short = reinterpret_cast<const uint32_t*>(ws + w.short_pos);
+        const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
+        const size_t plans = batch.plans.size();
+        std::vector<CrcGroupCall> full(plans), shrt(plans);
+        bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum);
+        for (size_t gi = 0; gi < plans; gi++) {
+            full[gi] = CrcGroupCall{&batch.plans[gi], lists.full_off[gi + 1] - lists.full_off[gi],
+                                    d_full + lists.full_off[gi]};
+            shrt[gi] = CrcGroupCall{&batch.plans[gi], lists.short_off[gi + 1] - lists.short_off[gi],
+                                    d_short + lists.short_off[gi]};
+            fused = fused && recon_crc_group_aligned(c, full[gi], d_shards, shard_strides, d_out, out_strides);
+        }
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, stream,
+                           [&](uint8_t* host) { write_rows_image(host, lists, w); });
+        if (rc != HEC_OK) return rc;
+        // 3. the full stripes as hec_reconstruct_crc_device_mixed runs them:
+        // one fused launch per pair ...
+        if (fused) {
+            for (const CrcGroupCall& call : full) {
+                if (call.stripes == 0) continue;
+                rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len, d_expected,
+                                     d_bad, d_sums, stream);
+                if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
+            }
+        } else if (!lists.full.empty()) {
+            // ... or the composition: verify per pair, one plain mixed call
+            // (the short stripes with nothing wanted), sums per pair
+            if (d_expected)
+                for (const CrcGroupCall& call : full) {
+                    if (call.stripes == 0) continue;
+                    rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides,
+                                             cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                    if (rc != HEC_OK) return rc;
+                }
+            std::vector<uint64_t> want_full;
+            if (!lists.shrt.empty()) {
+                want_full.resize(stripes);
+                for (size_t s = 0; s < stripes; s++)
+                    want_full[s] = rows_short(stripe_bytes[s], c->k, cell_len) ? 0 : (want ? want[s] : ~present[s]);
+            }
+            rc = mixed_reconstruct_impl(c, d_shards, shard_strides, d_out, out_strides, present,
+                                        want_full.empty() ? want : want_full.data(), cell_len, stripes, d_workspace,
+                                        w.full_pos, hip_stream);
+            if (rc != HEC_OK) return rc;
+            for (const CrcGroupCall& call : full) {
+                if (call.stripes == 0) continue;
+                rc = recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
+                                         bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                if (rc != HEC_OK) return rc;
+            }
+        }
+        // 4. one launch per pair over its short stripes
+        for (size_t gi = 0; gi < plans; gi++) {
+            rc = recon_rows_short(c, kind, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused,
+                                  d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
+                                  d_expected, d_bad, d_sums, stream);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;

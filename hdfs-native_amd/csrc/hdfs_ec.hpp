@@ -395,6 +395,63 @@ class Coder {
                                                 d_workspace, workspace_bytes, hip_stream));
     }
 
+    // Verified reconstruction of a group whose last stripe is short
+    // (hec_reconstruct_crc_rows_device): reconstruct_crc_device with data_len
+    // as for hec_composite_crc (0 = every stripe full).  In the last stripe
+    // every unit is verified, rebuilt and summed over its own bytes; a rebuilt
+    // slot is zero from its length up to n0 and nothing at or past n0 is
+    // written.  HEC_CHECKSUM_NULL is refused.
+    void reconstruct_crc_rows_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                     const std::vector<size_t>& strides, const std::vector<uint8_t*>& d_out,
+                                     const std::vector<size_t>& out_strides, const std::vector<size_t>* want,
+                                     size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                                     const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums,
+                                     void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units || d_out.size() != units || out_strides.size() != units)
+            throw std::invalid_argument("reconstruct_crc_rows_device: need data_units + parity_units slots");
+        std::vector<uint8_t> want_flags(units, 0);
+        if (want)
+            for (size_t t : *want) {
+                if (t >= units) throw std::invalid_argument("reconstruct_crc_rows_device: want index out of range");
+                want_flags[t] = 1;
+            }
+        check(hec_reconstruct_crc_rows_device(h_.get(), checksum_type, d_units.data(), strides.data(), d_out.data(),
+                                              out_strides.data(), want ? want_flags.data() : nullptr, cell_len,
+                                              stripes, bytes_per_checksum, data_len, d_expected, d_bad, d_sums,
+                                              hip_stream));
+    }
+    // One pattern and one length per stripe
+    // (hec_reconstruct_crc_rows_device_mixed): stripe_bytes (nullptr = every
+    // stripe full) holds the logical bytes of each stripe, 0 or k * cell_len =
+    // full; d_workspace of reconstruct_crc_rows_mixed_workspace_size(stripes)
+    // bytes, 8-byte aligned, untouched until the stream has passed the call.
+    size_t reconstruct_crc_rows_mixed_workspace_size(size_t stripes) const {
+        return hec_reconstruct_crc_rows_mixed_workspace_size(h_.get(), stripes);
+    }
+    void reconstruct_crc_rows_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                           const std::vector<size_t>& strides, const std::vector<uint8_t*>& d_out,
+                                           const std::vector<size_t>& out_strides,
+                                           const std::vector<uint64_t>& present, const std::vector<uint64_t>* want,
+                                           const std::vector<uint64_t>* stripe_bytes, size_t cell_len,
+                                           size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                           uint8_t* d_sums, void* d_workspace, size_t workspace_bytes,
+                                           void* hip_stream = nullptr) const {
+        const size_t units = k_ + m_;
+        if (d_units.size() != units || strides.size() != units || d_out.size() != units || out_strides.size() != units)
+            throw std::invalid_argument("reconstruct_crc_rows_device_mixed: need data_units + parity_units slots");
+        if (want && want->size() != present.size())
+            throw std::invalid_argument("reconstruct_crc_rows_device_mixed: one want mask per stripe");
+        if (stripe_bytes && stripe_bytes->size() != present.size())
+            throw std::invalid_argument("reconstruct_crc_rows_device_mixed: one length per stripe");
+        check(hec_reconstruct_crc_rows_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(),
+                                                    d_out.data(), out_strides.data(), present.data(),
+                                                    want ? want->data() : nullptr,
+                                                    stripe_bytes ? stripe_bytes->data() : nullptr, cell_len,
+                                                    present.size(), bytes_per_checksum, d_expected, d_bad, d_sums,
+                                                    d_workspace, workspace_bytes, hip_stream));
+    }
+
    private:
     ScrubResult make_result(const hec_scrub_result_t& r) const {
         ScrubResult s;

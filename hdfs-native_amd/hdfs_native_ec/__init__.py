@@ -66,6 +66,8 @@ EXPORTS = [
     "hec_reconstruct_mixed_workspace_size", "hec_reconstruct_device_mixed",
     "hec_reconstruct_crc_device", "hec_reconstruct_crc_mixed_workspace_size", "hec_reconstruct_crc_device_mixed",
     "hec_reconstruct_sums_device", "hec_reconstruct_sums_device_mixed",
+    "hec_reconstruct_crc_rows_device", "hec_reconstruct_crc_rows_mixed_workspace_size",
+    "hec_reconstruct_crc_rows_device_mixed",
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
@@ -195,6 +197,11 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_reconstruct_sums_device": ([P, I, PP, SP, P, S, S, S, ctypes.c_uint64, P, P, P, P], I),
         "hec_reconstruct_sums_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64),
                                                ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
+        "hec_reconstruct_crc_rows_device": ([P, I, PP, SP, PP, SP, P, S, S, S, ctypes.c_uint64, P, P, P, P], I),
+        "hec_reconstruct_crc_rows_mixed_workspace_size": ([P, S], S),
+        "hec_reconstruct_crc_rows_device_mixed": ([P, I, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64),
+                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                   S, S, S, P, P, P, P, S, P], I),
         "hec_scrub_verdict": ([ctypes.c_uint64, ctypes.c_uint64, S, ctypes.POINTER(I)], I),
         "hec_scrub": ([P, PP, S, P], I),
         "hec_scrub_device": ([P, PP, SP, S, S, P, P], I),
@@ -844,6 +851,44 @@ class Coder:
                                                            ctypes.c_void_p(workspace_ptr), workspace_bytes,
                                                            ctypes.c_void_p(stream)))
 
+    def reconstruct_crc_rows_device(self, shard_ptrs, shard_strides, out_ptrs, out_strides, cell_len, stripes,
+                                    sums_ptr, want=None, data_len: int = 0, expected_ptr=None, bad_ptr=None,
+                                    bytes_per_checksum: int = 512, checksum_type: int = CHECKSUM_CRC32C,
+                                    stream: int = 0) -> None:
+        """hec_reconstruct_crc_rows_device: reconstruct_crc_device for a group
+        whose last stripe is short.  data_len as for composite_crc (0 = every
+        stripe full): in the last stripe every unit is verified, rebuilt and
+        summed over its own bytes, a rebuilt slot is zero from there up to n0
+        and nothing at or past n0 is written."""
+        _check(self._lib.hec_reconstruct_crc_rows_device(self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]),
+                                                         _sp(shard_strides), _pp([p or 0 for p in out_ptrs]),
+                                                         _sp(out_strides), _want_bytes(len(shard_ptrs), want),
+                                                         cell_len, stripes, bytes_per_checksum, data_len,
+                                                         ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+                                                         ctypes.c_void_p(sums_ptr), ctypes.c_void_p(stream)))
+
+    def reconstruct_crc_rows_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_reconstruct_crc_rows_mixed_workspace_size(self._h, stripes)
+
+    def reconstruct_crc_rows_device_mixed(self, shard_ptrs, shard_strides, out_ptrs, out_strides, present_masks,
+                                          want_masks, stripe_bytes, cell_len, stripes, sums_ptr, workspace_ptr,
+                                          workspace_bytes, expected_ptr=None, bad_ptr=None,
+                                          bytes_per_checksum: int = 512, checksum_type: int = CHECKSUM_CRC32C,
+                                          stream: int = 0) -> None:
+        """hec_reconstruct_crc_rows_device_mixed: reconstruct_crc_device_mixed
+        with the logical bytes of every stripe (stripe_bytes[s]; None = all
+        full; 0 or k * cell_len = that stripe is full).  The workspace is
+        reconstruct_crc_rows_mixed_workspace_size(stripes) bytes, 8-byte
+        aligned."""
+        masks = (ctypes.c_uint64 * stripes)(*present_masks)
+        wants = None if want_masks is None else (ctypes.c_uint64 * stripes)(*want_masks)
+        lens = None if stripe_bytes is None else (ctypes.c_uint64 * stripes)(*stripe_bytes)
+        _check(self._lib.hec_reconstruct_crc_rows_device_mixed(
+            self._h, checksum_type, _pp(shard_ptrs), _sp(shard_strides), _pp([p or 0 for p in out_ptrs]),
+            _sp(out_strides), masks, wants, lens, cell_len, stripes, bytes_per_checksum,
+            ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr), ctypes.c_void_p(sums_ptr),
+            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)))
+
     def gf_matmul_device(self, matrix: List[List[int]], in_ptrs, in_strides, out_ptrs, out_strides, cell_len,
                          stripes, stream: int = 0) -> None:
         rows, cols = len(matrix), len(matrix[0])
@@ -1084,6 +1129,35 @@ def reconstruct_crc_batch_mixed(coder: Coder, cells, present_masks: Sequence[int
                                        expected_ptr=None if expected is None else expected.data_ptr(),
                                        bad_ptr=None if bad is None else bad.data_ptr(),
                                        checksum_type=checksum_type, stream=s.cuda_stream)
+    return workspace
+
+
+def reconstruct_crc_rows_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], sums, stripe_bytes=None,
+                                     want_masks=None, expected=None, bad=None, checksum_type: int = CHECKSUM_CRC32C,
+                                     bytes_per_checksum: int = 512, stream=None, workspace=None):
+    """reconstruct_crc_batch_mixed for a batch with short stripes:
+    stripe_bytes[s] = the logical bytes of stripe s (None = all full; 0 or
+    k * cell = that stripe is full).  In a short stripe every unit is verified,
+    rebuilt and summed over its own bytes, a rebuilt slot is zero from its
+    length up to n0 = min(cell, stripe_bytes[s]) and nothing at or past n0 is
+    written.  Returns the workspace (reusable once the stream has passed the
+    call)."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    nbytes = coder.reconstruct_crc_rows_mixed_workspace_size(S)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=cells.device)
+    coder.reconstruct_crc_rows_device_mixed(ptrs, strides, ptrs, strides, list(present_masks),
+                                            None if want_masks is None else list(want_masks),
+                                            None if stripe_bytes is None else list(stripe_bytes), cells.shape[2], S,
+                                            sums.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                            expected_ptr=None if expected is None else expected.data_ptr(),
+                                            bad_ptr=None if bad is None else bad.data_ptr(),
+                                            bytes_per_checksum=bytes_per_checksum, checksum_type=checksum_type,
+                                            stream=s.cuda_stream)
     return workspace
 
 

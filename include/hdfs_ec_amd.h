@@ -424,6 +424,89 @@ int hec_reconstruct_sums_device_mixed(hec_coder_t *coder, int checksum_type,
                                       const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums,
                                       void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* ---- Verified reconstruction of short stripes ------------------------------ *
+ * hec_reconstruct_crc_device / _mixed for stripes that hold fewer than
+ * k * cell_len logical bytes: the last stripe of a block group (data_len, the
+ * uniform form) or any stripe of a batch that spans groups or small files
+ * (stripe_bytes, the mixed form).  Shards, outputs, want, present, the
+ * survivors (the first k present units, whatever their length), plans,
+ * in-place repair, the [stripe][k+m][nck] layout of d_sums / d_expected with
+ * nck = ceil(cell_len / bytes_per_checksum), the [stripe][k+m] layout of d_bad,
+ * d_expected == d_sums, flags only ever set, asynchronous (no synchronisation,
+ * no allocation, no read-back), HEC_ERR_NOT_ENOUGH_SHARDS with nothing queued
+ * and HEC_ERR_DEVICE on a host-only coder are theirs.
+ *
+ * A stripe of r logical bytes, 1 <= r <= k*cell_len, has n0 = min(cell_len, r),
+ * data unit u < k of len(u) = min(cell_len, max(0, r - u*cell_len)) bytes and
+ * every parity unit of n0 bytes (the geometry of hec_composite_crc and
+ * hec_reconstruct_sums_device).
+ *   data_len (uniform form) has the meaning and the range check of
+ *     hec_composite_crc: 0 = every stripe full; otherwise only the last stripe
+ *     is short, r = data_len - (stripes-1)*k*cell_len.
+ *   stripe_bytes[stripes] (mixed form, host array, NULL = every stripe full):
+ *     an entry of 0 or k*cell_len says the stripe is full, any other entry is
+ *     the stripe's r; an entry above k*cell_len is HEC_ERR_INVALID_ARG.
+ * In a short stripe:
+ *   A present unit counts as zero from len(u) on: no slot byte at or past
+ *     len(u) influences any output, a present unit of length 0 is not read at
+ *     all and none of its sums words is read.  Nothing at or past cell_len of a
+ *     slot is read; on the 16-B aligned route a read may reach the end of the
+ *     16-byte block that holds byte n0-1, and no further.
+ *   With d_expected each survivor the plan reads is verified over its own
+ *     len(u) bytes: chunks c < ceil(len(u) / bytes_per_checksum), the last one
+ *     short; sums slots past that are not read.
+ *   A rebuilt unit t gets its len(t) computed bytes at [0, len(t)) and zeros at
+ *     [len(t), n0): the slot is what CellReader::next_cell hands out, and
+ *     hec_scrub_device with cell_len = n0 on that stripe sees a consistent
+ *     stripe.  No byte at or past n0 of any slot is written.
+ *   The sums of t are written for chunks c < ceil(len(t) / bytes_per_checksum),
+ *     the last over [c*bpc, len(t)); the slots past that -- all of them when
+ *     len(t) == 0 -- are not written.  These are the sums hec_composite_crc*
+ *     expects: a repaired group's block and group CRCs are this call and
+ *     hec_composite_crc_device with the same data_len, on one stream and one
+ *     sums array.
+ *   A stripe with a flagged survivor gets unspecified content in its targets'
+ *     [0, n0) and in their live sums words; everything else holds.
+ * HEC_CHECKSUM_NULL is HEC_ERR_INVALID_ARG: without sums a short stripe needs
+ * no call of its own, because zero-padded slots through
+ * hec_reconstruct_device[_mixed] give the same bytes.  The other
+ * HEC_ERR_INVALID_ARG cases (nothing queued) are those of
+ * hec_reconstruct_crc_device[_mixed], plus data_len out of range and a
+ * stripe_bytes entry out of range; the coder, the checksum type, cell_len,
+ * bytes_per_checksum, data_len and stripe_bytes are checked before the coder's
+ * device.  HEC_OK, nothing queued: stripes == 0 or no target anywhere.
+ * Full stripes make exactly the launches of hec_reconstruct_crc_device[_mixed]
+ * (with data_len == 0 / stripe_bytes == NULL every output byte is theirs).
+ * Short stripes run a one-pass kernel (k reads, t writes and their sums over
+ * [0, n0)) for k in {2,3,6,10}, at most 4 target rows per pattern,
+ * bytes_per_checksum == 512 and 16-B aligned bases, strides and cell_len -- the
+ * lengths themselves may be any byte count -- and a byte-wise kernel with the
+ * same results for every other shape.  Uniform form: one launch over the
+ * stripes-1 full stripes, one over the last; kernels only, capturable into a
+ * graph.  Mixed form: per distinct (present, want) pair one launch over its
+ * full stripes and one over its short stripes.  Its workspace
+ * (hec_reconstruct_crc_rows_mixed_workspace_size, never smaller than
+ * hec_reconstruct_crc_mixed_workspace_size) is always required, 8-byte
+ * aligned, and holds the short stripes' lists and lengths behind what
+ * hec_reconstruct_crc_device_mixed keeps there; it stays untouched until the
+ * stream reaches the work, and calls in flight at once need different
+ * workspaces. */
+int hec_reconstruct_crc_rows_device(hec_coder_t *coder, int checksum_type,
+                                    const uint8_t *const *d_shards, const size_t *shard_strides,
+                                    uint8_t *const *d_out, const size_t *out_strides, const uint8_t *want,
+                                    size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                                    const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums, void *hip_stream);
+
+size_t hec_reconstruct_crc_rows_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+
+int hec_reconstruct_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
+                                          const uint8_t *const *d_shards, const size_t *shard_strides,
+                                          uint8_t *const *d_out, const size_t *out_strides,
+                                          const uint64_t *present, const uint64_t *want, const uint64_t *stripe_bytes,
+                                          size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                          const uint8_t *d_expected, uint8_t *d_bad, uint8_t *d_sums,
+                                          void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* ---- Scrub: verify a stripe's parity and locate a corrupt unit ----------- *
  * What a block scanner or a repair worker asks before and after it rebuilds
  * (`hdfs debug verifyEC`; dfs.datanode.ec.reconstruct.validation, HDFS-15759):

@@ -122,6 +122,19 @@ unsafe extern "C" {
                                          d_expected: *const u8, d_bad: *mut u8, d_sums: *mut u8,
                                          d_workspace: *mut c_void, workspace_bytes: usize,
                                          stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_crc_rows_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                       shard_strides: *const usize, d_out: *const *mut u8,
+                                       out_strides: *const usize, want: *const u8, cell_len: usize, stripes: usize,
+                                       bytes_per_checksum: usize, data_len: u64, d_expected: *const u8,
+                                       d_bad: *mut u8, d_sums: *mut u8, stream: *mut c_void) -> c_int;
+    fn hec_reconstruct_crc_rows_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_reconstruct_crc_rows_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                             shard_strides: *const usize, d_out: *const *mut u8,
+                                             out_strides: *const usize, present: *const u64, want: *const u64,
+                                             stripe_bytes: *const u64, cell_len: usize, stripes: usize,
+                                             bytes_per_checksum: usize, d_expected: *const u8, d_bad: *mut u8,
+                                             d_sums: *mut u8, d_workspace: *mut c_void, workspace_bytes: usize,
+                                             stream: *mut c_void) -> c_int;
     fn hec_scrub_verdict(ruled_out: u64, bad_bytes: u64, units: usize, unit: *mut c_int) -> c_int;
     fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
     fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
@@ -468,6 +481,76 @@ impl GpuCoder {
                                               want.map_or(std::ptr::null(), |w| w.as_ptr()), cell, present.len(),
                                               bytes_per_checksum, expected, bad, sums, workspace, workspace_bytes,
                                               stream)
+        })
+    }
+
+    /// `reconstruct_crc_device` for a block group whose last stripe is short
+    /// (`hec_reconstruct_crc_rows_device`).  `data_len` as for
+    /// `hec_composite_crc`: 0 = every stripe full, otherwise the last stripe
+    /// holds the file's tail.  There every survivor counts as zero from its own
+    /// length on and is verified over its own bytes, a rebuilt unit gets its
+    /// bytes, zeros up to n0 = min(cell, tail) and the sums of its own bytes,
+    /// and nothing at or past n0 is written: the slots are what
+    /// `CellReader::next_cell` hands out and `sums` is what
+    /// `hec_composite_crc_device` with the same `data_len` folds into the block
+    /// and group CRCs.  `checksum_type` is CRC32C or CRC32.
+    ///
+    /// # Safety
+    /// As `reconstruct_crc_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_crc_rows_device(&self, checksum_type: i32, shards: &[*const u8],
+                                              shard_strides: &[usize], out: &[*mut u8], out_strides: &[usize],
+                                              want: Option<&[usize]>, cell: usize, stripes: usize,
+                                              bytes_per_checksum: usize, data_len: u64, expected: *const u8,
+                                              bad: *mut u8, sums: *mut u8, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        let flags = want.map(|w| want_flags(n, w));
+        check(unsafe {
+            hec_reconstruct_crc_rows_device(self.raw, checksum_type as c_int, shards.as_ptr(),
+                                            shard_strides.as_ptr(), out.as_ptr(), out_strides.as_ptr(),
+                                            flags.as_ref().map_or(std::ptr::null(), |f| f.as_ptr()), cell, stripes,
+                                            bytes_per_checksum, data_len, expected, bad, sums, stream)
+        })
+    }
+
+    /// Device bytes `reconstruct_crc_rows_device_mixed` needs for `stripes` stripes.
+    pub fn reconstruct_crc_rows_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_reconstruct_crc_rows_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// A repair batch that spans block groups or small files
+    /// (`hec_reconstruct_crc_rows_device_mixed`): `reconstruct_crc_device_mixed`
+    /// with the logical bytes of every stripe.  `stripe_bytes[s]` of 0 or
+    /// `k * cell` says stripe `s` is full (`None`: all of them); any other
+    /// value is the stripe's length, handled as the last stripe of
+    /// `reconstruct_crc_rows_device`.  `workspace` is device memory of
+    /// `reconstruct_crc_rows_mixed_workspace_size(stripes)` bytes, 8-byte
+    /// aligned, untouched until `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `reconstruct_crc_device_mixed`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn reconstruct_crc_rows_device_mixed(&self, checksum_type: i32, shards: &[*const u8],
+                                                    shard_strides: &[usize], out: &[*mut u8],
+                                                    out_strides: &[usize], present: &[u64], want: Option<&[u64]>,
+                                                    stripe_bytes: Option<&[u64]>, cell: usize,
+                                                    bytes_per_checksum: usize, expected: *const u8, bad: *mut u8,
+                                                    sums: *mut u8, workspace: *mut c_void, workspace_bytes: usize,
+                                                    stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(out.len() == n && out_strides.len() == n, "one output slot per unit");
+        assert!(want.map_or(true, |w| w.len() == present.len()), "one want mask per stripe");
+        assert!(stripe_bytes.map_or(true, |b| b.len() == present.len()), "one length per stripe");
+        check(unsafe {
+            hec_reconstruct_crc_rows_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(),
+                                                  shard_strides.as_ptr(), out.as_ptr(), out_strides.as_ptr(),
+                                                  present.as_ptr(), want.map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                  stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()), cell,
+                                                  present.len(), bytes_per_checksum, expected, bad, sums, workspace,
+                                                  workspace_bytes, stream)
         })
     }
 
