@@ -41,6 +41,7 @@
 #include "ec_reconstruct_rows.hpp"
 #include "ec_reconstruct_sums.hpp"
 #include "ec_scrub_crc.hpp"
+#include "ec_scrub_rows.hpp"
 #include "gf256.hpp"
 #include "host_gf.hpp"
 #include "jit.hpp"
@@ -3448,10 +3449,11 @@ struct ScrubCrcGroup {
     const uint32_t* d_list;  // null: stripes 0 .. stripes-1
 };
 
-// The fused launch of one group.  0 ok, -1 refused by the launcher, else HEC_*.
+// The fused launch of one group; with `lens`, of its short stripes
+// (gf_scrub_crc_rows).  0 ok, -1 refused by the launcher, else HEC_*.
 int scrub_crc_fused(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_t* const* d_shards,
                     const size_t* shard_strides, size_t cell_len, const uint8_t* d_expected, uint8_t* d_bad,
-                    hec_scrub_result_t* d_results, hipStream_t stream) {
+                    hec_scrub_result_t* d_results, hipStream_t stream, const hec::ReconRowsLens* lens = nullptr) {
     const size_t k = c->k, n = c->k + c->m;
     const DecodePlan& p = *g.sp->plan;
     hec::MatmulArgs a;
@@ -3482,7 +3484,8 @@ int scrub_crc_fused(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_
     cs.n_total = uint32_t(n);
     cs.kind = kind;
     cs.stripe_list = g.d_list;
-    const int rc = hec::launch_scrub_crc(a, cs, c->device, stream);
+    const int rc = lens ? hec::launch_scrub_crc_rows(a, cs, *lens, c->device, stream)
+                        : hec::launch_scrub_crc(a, cs, c->device, stream);
     if (rc <= 0) return rc;
     return to_status(rc);
 }
@@ -3645,6 +3648,306 @@ int hec_scrub_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t*
         }
         return hec_scrub_device_mixed(c, d_shards, shard_strides, present, cell_len, stripes, d_results, d_workspace,
                                       lists_pos, hip_stream);
+    });
+}
+
+// ---- verified scrub of short stripes ------------------------------------------
+// hec_scrub_crc_rows_device*: hec_scrub_crc_device* with the lengths of
+// hec_reconstruct_crc_rows_device* -- a stripe of r < k * cell_len logical
+// bytes is checked over its positions below n0 and every present unit is
+// verified over its own bytes (ec_scrub_rows.hip).  Full stripes run as the
+// existing calls run them, launch for launch.
+
+}  // extern "C"
+
+namespace {
+
+// hec_scrub_crc_device_mixed's groups as one Batch, so that rows_lists splits
+// every group's stripes into full and short: a plan per distinct mask with an
+// extra, in the order the masks first appear, then an entry without rows (sums
+// only; `missing` = the units the mask lacks) per distinct mask without an
+// extra that still has a unit.  *fits: every check plan is within the fused
+// kernel's rows and pivots.  Host only, nothing queued.
+int scrub_rows_groups(hec_coder* c, const uint64_t* present, size_t stripes, Batch* b, bool* fits) {
+    const uint64_t all = unit_bits(c->k + c->m);
+    *fits = true;
+    const int rc = group_stripes(
+        c, present, stripes, kNoPlanId, [](size_t, uint64_t) { return uint64_t(0); },
+        [&](uint64_t mask, uint64_t, RowPlan* sp) {
+            const int src = scrub_rows(c, mask, sp);
+            if (src != HEC_OK || sp->rows.empty()) return src;
+            *fits = *fits && scrub_crc_plan_fits(c, *sp);
+            return int(HEC_OK);
+        },
+        b);
+    if (rc != HEC_OK) return rc;
+    std::map<uint64_t, uint32_t> bare;  // e == 0: mask -> its entry
+    for (size_t s = 0; s < stripes; s++) {
+        const uint64_t mask = present[s] & all;
+        if (b->stripe_plan[s] != kNoPlanId || !mask) continue;
+        auto it = bare.find(mask);
+        if (it == bare.end()) {
+            RowPlan rp;
+            rp.missing = ~mask & all;
+            it = bare.emplace(mask, uint32_t(b->plans.size())).first;
+            b->plans.push_back(std::move(rp));
+        }
+        b->stripe_plan[s] = it->second;
+    }
+    return HEC_OK;
+}
+
+// rows_layout behind hec_scrub_crc_device_mixed's workspace: the full
+// stripes' lists where that call keeps its lists, then, behind its whole
+// workspace, [short lists: u32][pad to kAlign][their bytes: u64].
+RowsLayout scrub_rows_layout(size_t k, size_t m, size_t stripes, size_t n_full, size_t n_short) {
+    RowsLayout w;
+    w.full_pos = align_up(scrub_workspace(k, m, stripes));
+    w.short_pos = align_up(scrub_crc_workspace(k, m, stripes));
+    w.bytes_pos = w.short_pos + align_up(n_short * sizeof(uint32_t));
+    w.need = n_short ? w.bytes_pos + n_short * sizeof(uint64_t) : w.full_pos + n_full * sizeof(uint32_t);
+    w.image_bytes = w.need - w.full_pos;
+    return w;
+}
+
+// The worst batch of `stripes`: every stripe short.
+size_t scrub_rows_workspace(size_t k, size_t m, size_t stripes) {
+    return scrub_rows_layout(k, m, stripes, 0, stripes).bytes_pos + stripes * sizeof(uint64_t);
+}
+
+// The shapes gf_scrub_crc_rows takes: gf_scrub_crc's, with lengths in 32 bits.
+bool scrub_rows_shape(const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
+                      size_t stripes, size_t bpc) {
+    return cell_len <= 0x7FFFFFFFull && scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bpc);
+}
+
+// The short stripes of one group (g.stripes of them, g.d_list or lens.stripe0
+// on): gf_scrub_crc_rows where `fused`, the group has a check plan and the
+// launcher takes it, else gf_scrub_rows_bytes (also all there is for a group
+// with e == 0: the units' sums over their own bytes).
+int scrub_rows_short(hec_coder* c, int kind, const ScrubCrcGroup& g, const hec::ReconRowsLens& lens, bool fused,
+                     const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len, size_t bpc,
+                     const uint8_t* d_expected, uint8_t* d_bad, hec_scrub_result_t* d_results, hipStream_t stream) {
+    if (g.stripes == 0) return HEC_OK;
+    const size_t k = c->k, n = c->k + c->m;
+    if (fused && g.sp) {
+        const int rc = scrub_crc_fused(c, kind, g, d_shards, shard_strides, cell_len, d_expected, d_bad, d_results,
+                                       stream, &lens);
+        if (rc != -1) return rc;  // -1: refused, nothing launched
+    }
+    hec::ScrubRowsBytesArgs a;
+    std::memset(&a, 0, sizeof(a));
+    size_t cnt = 0;
+    if (g.sp) {
+        const DecodePlan& p = *g.sp->plan;
+        if (g.sp->rows.size() > size_t(hec::kScrubRowsMaxE)) return HEC_ERR_INVALID_ARG;
+        for (size_t r = 0; r < k; r++) {
+            const size_t u = p.rec_survivors[r];
+            a.in[cnt] = d_shards[u];
+            a.in_stride[cnt] = shard_strides[u];
+            a.id[cnt++] = uint8_t(u);
+        }
+        a.ns = int32_t(k);
+        for (size_t j = 0; j < g.sp->rows.size(); j++) {
+            const size_t row = g.sp->rows[j], u = p.lost[row];
+            a.in[cnt] = d_shards[u];
+            a.in_stride[cnt] = shard_strides[u];
+            a.id[cnt++] = uint8_t(u);
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+        }
+        a.e = int32_t(g.sp->rows.size());
+        a.missing = g.sp->missing;
+    } else {
+        for (size_t u = 0; u < n; u++) {
+            if (!((g.mask >> u) & 1)) continue;
+            a.in[cnt] = d_shards[u];
+            a.in_stride[cnt] = shard_strides[u];
+            a.id[cnt++] = uint8_t(u);
+        }
+        if (cnt == 0) return HEC_OK;
+        a.ns = int32_t(cnt);
+    }
+    a.data_units = uint32_t(k);
+    a.n_total = uint32_t(n);
+    a.expected = d_expected;
+    a.bad = d_bad;
+    a.results = reinterpret_cast<uint64_t*>(d_results);
+    a.kind = kind;
+    a.stripe_list = g.d_list;
+    a.stripes = g.stripes;
+    a.lens = lens;
+    a.cell_len = cell_len;
+    a.bytes_per_checksum = bpc;
+    const int rc = hec::launch_scrub_rows_bytes(a, c->device, stream);
+    if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+    return HEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_scrub_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                              const size_t* shard_strides, size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                              uint64_t data_len, const uint8_t* d_expected, uint8_t* d_bad,
+                              hec_scrub_result_t* d_results, void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    hec::crc::Geometry geo;
+    if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
+        return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_rows_device");
+    chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum, d_expected,
+                          d_bad, d_results, &kind);
+    if (chk != HEC_OK) return chk;
+    // every stripe full: the existing call, launch for launch
+    if (stripes == 0 || geo.last_len == uint64_t(c->k) * cell_len)
+        return hec_scrub_crc_device(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
+                                    d_expected, d_bad, d_results, hip_stream);
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        const uint64_t all = unit_bits(c->k + c->m);
+        RowPlan sp;
+        const int prc = scrub_rows(c, all, &sp);
+        if (prc != HEC_OK) return prc;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const RowPlan* plan = sp.rows.empty() ? nullptr : &sp;
+        bool fused = plan && scrub_crc_plan_fits(c, sp) &&
+                     scrub_rows_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        // one launch over the stripes - 1 full stripes, one over the last;
+        // the results are zeroed once, in stream order (a zeroing kernel node
+        // under capture)
+        if (fused) {
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            if (stripes > 1) {
+                const int rc = scrub_crc_fused(c, kind, ScrubCrcGroup{all, plan, stripes - 1, nullptr}, d_shards,
+                                               shard_strides, cell_len, d_expected, d_bad, d_results, stream);
+                if (rc == -1) fused = false;  // refused, no kernel launched
+                else if (rc != HEC_OK) return rc;
+            }
+        }
+        if (!fused) {
+            // the composition zeroes its own stripes' results
+            if (stripes > 1) {
+                const int rc = hec_scrub_crc_device(c, checksum_type, d_shards, shard_strides, cell_len, stripes - 1,
+                                                    bytes_per_checksum, d_expected, d_bad, d_results, hip_stream);
+                if (rc != HEC_OK) return rc;
+            }
+            HEC_HIP(hec::zero_async(d_results + (stripes - 1), sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        }
+        return scrub_rows_short(c, kind, ScrubCrcGroup{all, plan, 1, nullptr},
+                                hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused, d_shards, shard_strides,
+                                cell_len, bytes_per_checksum, d_expected, d_bad, d_results, stream);
+    });
+}
+
+size_t hec_scrub_crc_rows_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return scrub_rows_workspace(c->k, c->m, stripes);
+}
+
+int hec_scrub_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                    const size_t* shard_strides, const uint64_t* present,
+                                    const uint64_t* stripe_bytes, size_t cell_len, size_t stripes,
+                                    size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                    hec_scrub_result_t* d_results, void* d_workspace, size_t workspace_bytes,
+                                    void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    bool any_short = false;
+    for (size_t s = 0; stripe_bytes && s < stripes; s++) {
+        if (stripe_bytes[s] > uint64_t(c->k) * cell_len) return HEC_ERR_INVALID_ARG;
+        any_short = any_short || rows_short(stripe_bytes[s], c->k, cell_len);
+    }
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_rows_device_mixed");
+    chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum, d_expected,
+                          d_bad, d_results, &kind);
+    if (chk != HEC_OK || !present) return chk != HEC_OK ? chk : HEC_ERR_INVALID_ARG;
+    // every stripe full: the existing call, launch for launch
+    if (stripes == 0 || !any_short)
+        return hec_scrub_crc_device_mixed(c, checksum_type, d_shards, shard_strides, present, cell_len, stripes,
+                                          bytes_per_checksum, d_expected, d_bad, d_results, d_workspace,
+                                          workspace_bytes, hip_stream);
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        const size_t k = c->k, m = c->m;
+        const uint64_t all = unit_bits(k + m);
+        // 1. the groups and their plans (host); fail before anything is queued
+        Batch batch;
+        bool fits = true;
+        int rc = scrub_rows_groups(c, present, stripes, &batch, &fits);
+        if (rc != HEC_OK) return rc;
+        const bool idle = batch.plans.empty();  // no stripe has a unit
+        if (!idle && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 15u) != 0 ||
+                      workspace_bytes < scrub_rows_workspace(k, m, stripes)))
+            return HEC_ERR_INVALID_ARG;
+        // 2. every group's full stripes and short stripes, the short ones' bytes
+        RowsLists lists;
+        rows_lists(batch, stripe_bytes, k, cell_len, &lists);
+        const RowsLayout w = scrub_rows_layout(k, m, stripes, lists.full.size(), lists.shrt.size());
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const bool fused = fits && scrub_rows_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        const bool composed = !fused && !lists.full.empty();  // the plain mixed scrub zeroes the results itself
+        if (!composed)
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+        if (idle) return HEC_OK;
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, stream,
+                           [&](uint8_t* host) { write_rows_image(host, lists, w); });
+        if (rc != HEC_OK) return rc;
+        const uint32_t* d_full = reinterpret_cast<const uint32_t*>(ws + w.full_pos);
+        const uint32_t* d_short = reinterpret_cast<const uint32_t*>(ws + w.short_pos);
+        const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
+        const size_t groups = batch.plans.size();
+        std::vector<ScrubCrcGroup> full(groups), shrt(groups);
+        for (size_t gi = 0; gi < groups; gi++) {
+            const RowPlan* sp = batch.plans[gi].rows.empty() ? nullptr : &batch.plans[gi];
+            const uint64_t mask = all & ~batch.plans[gi].missing;
+            full[gi] = ScrubCrcGroup{mask, sp, lists.full_off[gi + 1] - lists.full_off[gi], d_full + lists.full_off[gi]};
+            shrt[gi] =
+                ScrubCrcGroup{mask, sp, lists.short_off[gi + 1] - lists.short_off[gi], d_short + lists.short_off[gi]};
+        }
+        // 3. the full stripes as hec_scrub_crc_device_mixed runs them: one
+        // launch per mask, the fused kernel or sums only where e == 0 ...
+        if (fused) {
+            for (const ScrubCrcGroup& grp : full) {
+                if (grp.stripes == 0) continue;
+                rc = grp.sp ? scrub_crc_fused(c, kind, grp, d_shards, shard_strides, cell_len, d_expected, d_bad,
+                                              d_results, stream)
+                            : scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum,
+                                               d_expected, d_bad, stream);
+                if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
+            }
+        } else if (composed) {
+            // ... or the composition: verify per mask, then the plain mixed
+            // scrub with the short stripes masked out (no unit: unchecked)
+            for (const ScrubCrcGroup& grp : full) {
+                if (grp.stripes == 0) continue;
+                rc = scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
+                                      d_bad, stream);
+                if (rc != HEC_OK) return rc;
+            }
+            std::vector<uint64_t> present_full(stripes);
+            for (size_t s = 0; s < stripes; s++)
+                present_full[s] = rows_short(stripe_bytes[s], k, cell_len) ? 0 : present[s];
+            rc = hec_scrub_device_mixed(c, d_shards, shard_strides, present_full.data(), cell_len, stripes, d_results,
+                                        d_workspace, w.full_pos, hip_stream);
+            if (rc != HEC_OK) return rc;
+        }
+        // 4. one launch per mask over its short stripes
+        for (size_t gi = 0; gi < groups; gi++) {
+            rc = scrub_rows_short(c, kind, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused,
+                                  d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected, d_bad, d_results,
+                                  stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return HEC_OK;
     });
 }
 

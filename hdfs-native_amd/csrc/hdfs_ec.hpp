@@ -304,6 +304,43 @@ class Coder {
                                          d_workspace, workspace_bytes, hip_stream));
     }
 
+    // Verified scrub of a group whose last stripe is short
+    // (hec_scrub_crc_rows_device): scrub_crc_device with data_len as for
+    // composite_crc_device (0 = every stripe full); the last stripe is checked
+    // over its positions below n0 and every unit verified over its own bytes.
+    void scrub_crc_rows_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                               const std::vector<size_t>& strides, size_t cell_len, size_t stripes,
+                               size_t bytes_per_checksum, uint64_t data_len, const uint8_t* d_expected,
+                               uint8_t* d_bad, hec_scrub_result_t* d_results, void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_crc_rows_device: need data_units + parity_units units");
+        check(hec_scrub_crc_rows_device(h_.get(), checksum_type, d_units.data(), strides.data(), cell_len, stripes,
+                                        bytes_per_checksum, data_len, d_expected, d_bad, d_results, hip_stream));
+    }
+    // One presence mask and one length per stripe
+    // (hec_scrub_crc_rows_device_mixed): stripe_bytes (nullptr = every stripe
+    // full) holds present.size() entries, 0 or k * cell_len = that stripe is
+    // full; d_workspace of scrub_crc_rows_mixed_workspace_size(stripes) bytes,
+    // 16-byte aligned, untouched until the stream has passed the call.
+    size_t scrub_crc_rows_mixed_workspace_size(size_t stripes) const {
+        return hec_scrub_crc_rows_mixed_workspace_size(h_.get(), stripes);
+    }
+    void scrub_crc_rows_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                     const std::vector<size_t>& strides, const std::vector<uint64_t>& present,
+                                     const std::vector<uint64_t>* stripe_bytes, size_t cell_len,
+                                     size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                     hec_scrub_result_t* d_results, void* d_workspace, size_t workspace_bytes,
+                                     void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_crc_rows_device_mixed: need data_units + parity_units units");
+        if (stripe_bytes && stripe_bytes->size() != present.size())
+            throw std::invalid_argument("scrub_crc_rows_device_mixed: one length per stripe");
+        check(hec_scrub_crc_rows_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(), present.data(),
+                                              stripe_bytes ? stripe_bytes->data() : nullptr, cell_len, present.size(),
+                                              bytes_per_checksum, d_expected, d_bad, d_results, d_workspace,
+                                              workspace_bytes, hip_stream));
+    }
+
     // Verified reconstruction of a device-resident batch, asynchronous on
     // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
     // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and

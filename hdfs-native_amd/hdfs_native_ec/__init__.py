@@ -71,6 +71,7 @@ EXPORTS = [
     "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
+    "hec_scrub_crc_rows_device", "hec_scrub_crc_rows_mixed_workspace_size", "hec_scrub_crc_rows_device_mixed",
     "hec_crc_concat", "hec_composite_crc", "hec_composite_crc_workspace_size", "hec_composite_crc_device",
 ]
 
@@ -212,6 +213,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_crc_device": ([P, I, PP, SP, S, S, S, P, P, P, P], I),
         "hec_scrub_crc_mixed_workspace_size": ([P, S], S),
         "hec_scrub_crc_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
+        "hec_scrub_crc_rows_device": ([P, I, PP, SP, S, S, S, ctypes.c_uint64, P, P, P, P], I),
+        "hec_scrub_crc_rows_mixed_workspace_size": ([P, S], S),
+        "hec_scrub_crc_rows_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
         "hec_crc_concat": ([I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)], I),
         "hec_composite_crc": ([I, P, S, S, S, S, S, ctypes.c_uint64, P, P, P], I),
         "hec_composite_crc_workspace_size": ([S, S], S),
@@ -684,6 +689,37 @@ class Coder:
                                                     ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
                                                     ctypes.c_void_p(results_ptr), ctypes.c_void_p(workspace_ptr),
                                                     workspace_bytes, ctypes.c_void_p(stream)))
+
+    def scrub_crc_rows_device(self, shard_ptrs, shard_strides, cell_len, stripes, expected_ptr, bad_ptr, results_ptr,
+                              data_len: int = 0, bytes_per_checksum: int = 512,
+                              checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_scrub_crc_rows_device: scrub_crc_device for a group whose last
+        stripe is short.  data_len as for composite_crc (0 = every stripe
+        full): the last stripe is checked over its positions below n0 and
+        every unit is verified over its own bytes."""
+        _check(self._lib.hec_scrub_crc_rows_device(self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]),
+                                                   _sp(shard_strides), cell_len, stripes, bytes_per_checksum,
+                                                   data_len, ctypes.c_void_p(expected_ptr),
+                                                   ctypes.c_void_p(bad_ptr), ctypes.c_void_p(results_ptr),
+                                                   ctypes.c_void_p(stream)))
+
+    def scrub_crc_rows_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_scrub_crc_rows_mixed_workspace_size(self._h, stripes)
+
+    def scrub_crc_rows_device_mixed(self, shard_ptrs, shard_strides, present_masks, stripe_bytes, cell_len, stripes,
+                                    expected_ptr, bad_ptr, results_ptr, workspace_ptr, workspace_bytes,
+                                    bytes_per_checksum: int = 512, checksum_type: int = CHECKSUM_CRC32C,
+                                    stream: int = 0) -> None:
+        """hec_scrub_crc_rows_device_mixed: scrub_crc_device_mixed with the
+        logical bytes of every stripe (stripe_bytes[s]; None = all full; 0 or
+        k * cell_len = that stripe is full).  The workspace is
+        scrub_crc_rows_mixed_workspace_size(stripes) bytes, 16-byte aligned."""
+        masks = None if present_masks is None else (ctypes.c_uint64 * max(stripes, 1))(*present_masks)
+        lens = None if stripe_bytes is None else (ctypes.c_uint64 * max(stripes, 1))(*stripe_bytes)
+        _check(self._lib.hec_scrub_crc_rows_device_mixed(
+            self._h, checksum_type, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides), masks, lens, cell_len,
+            stripes, bytes_per_checksum, ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+            ctypes.c_void_p(results_ptr), ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)))
 
     def prepare_decode(self, missing: Sequence[int], checksum_type: int = 2) -> bool:
         """hec_coder_prepare_decode: compile the plan-specialised fused decode
@@ -1277,6 +1313,38 @@ def scrub_crc_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], exp
     coder.scrub_crc_device_mixed(ptrs, strides, list(present_masks), cells.shape[2], S, expected.data_ptr(),
                                  bad.data_ptr(), out.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                  checksum_type=checksum_type, stream=s.cuda_stream)
+    return out, bad
+
+
+def scrub_crc_rows_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], expected, stripe_bytes=None,
+                               bad=None, checksum_type: int = CHECKSUM_CRC32C, bytes_per_checksum: int = 512,
+                               stream=None, workspace=None):
+    """scrub_crc_batch_mixed for a batch with short stripes: stripe_bytes[s] =
+    the logical bytes of stripe s (None = all full; 0 or k * cell = that stripe
+    is full).  A short stripe is checked over its positions below n0 =
+    min(cell, stripe_bytes[s]) with every unit zero from its own length on, and
+    every present unit is verified over its own bytes.  -> (results, bad) as
+    scrub_crc_batch_mixed.  Pass `workspace` (uint8 cuda tensor of
+    coder.scrub_crc_rows_mixed_workspace_size(S) bytes) to reuse one; it must
+    stay untouched until the stream has passed the call."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    with torch.cuda.stream(s):
+        out = torch.empty((S, 2), dtype=torch.int64, device=cells.device)
+        if bad is None:
+            bad = torch.zeros((S, n), dtype=torch.uint8, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    if workspace is None:
+        workspace = torch.empty(max(coder.scrub_crc_rows_mixed_workspace_size(S), 1), dtype=torch.uint8,
+                                device=cells.device)
+        workspace.record_stream(s)
+    coder.scrub_crc_rows_device_mixed(ptrs, strides, list(present_masks),
+                                      None if stripe_bytes is None else list(stripe_bytes), cells.shape[2], S,
+                                      expected.data_ptr(), bad.data_ptr(), out.data_ptr(), workspace.data_ptr(),
+                                      workspace.numel(), bytes_per_checksum=bytes_per_checksum,
+                                      checksum_type=checksum_type, stream=s.cuda_stream)
     return out, bad
 
 

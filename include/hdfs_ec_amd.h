@@ -722,6 +722,81 @@ int hec_scrub_crc_device_mixed(hec_coder_t *coder, int checksum_type,
                                hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
                                void *hip_stream);
 
+/* ---- Verified scrub of short stripes -------------------------------------- *
+ * hec_scrub_crc_device / hec_scrub_crc_device_mixed with the lengths of
+ * hec_reconstruct_crc_rows_device[_mixed]: the last stripe of a block group
+ * (data_len) or every stripe of a batch of small files (stripe_bytes) holds
+ * r < k*cell_len logical bytes.  A short group is repaired and checked with
+ * hec_reconstruct_crc_rows_device* -> hec_scrub_crc_rows_device* ->
+ * hec_composite_crc_device on one stream and one sums array, without padding
+ * by the caller and without per-stripe calls.  Everything not said here is
+ * what hec_scrub_crc_device[_mixed] does: shards, masks, survivors S and extras
+ * E, d_results zeroed by the call on the stream (a zeroing kernel node under
+ * capture), missing-unit bits and the (0, 0) of unchecked stripes, flags that
+ * are only ever set, read-only over the cells and d_expected, asynchronous,
+ * no allocation, no read-back, HEC_ERR_DEVICE on a host-only coder.
+ * Geometry: a stripe holds r logical bytes, 1 <= r <= k*cell_len; n0 =
+ * min(cell_len, r); data unit u holds len(u) = min(cell_len, max(0, r -
+ * u*cell_len)) bytes and every parity unit n0 bytes.
+ *   data_len (uniform form) has the meaning and the range check of
+ *     hec_composite_crc: 0 = every stripe full; otherwise only the last stripe
+ *     is short.
+ *   stripe_bytes[stripes] (mixed form, host array, NULL = every stripe full):
+ *     an entry of 0 or k*cell_len says the stripe is full; an entry above
+ *     k*cell_len is HEC_ERR_INVALID_ARG.
+ *   d_expected stays [stripe][k+m][nck], nck = ceil(cell_len /
+ *     bytes_per_checksum); d_bad stays [stripe][k+m].
+ * In a short stripe:
+ *   d_results[s] is exactly what hec_scrub_degraded returns for that stripe
+ *     with shard_len = n0 when every present unit is its own len(u) bytes
+ *     followed by zeros up to n0 -- what hec_scrub_device[_mixed] returns with
+ *     cell_len = n0 on zero-padded slots.  Only positions b < n0 are checked or
+ *     counted; a position at or past len(u) does not additionally rule u out.
+ *   A present unit counts as zero from len(u) on: no slot byte at or past
+ *     len(u) influences a result or a flag, a present unit of length 0 is not
+ *     read at all and none of its sums words is read.  Nothing at or past
+ *     cell_len of a slot is read; on the 16-B aligned route a read may reach the
+ *     end of the 16-byte block that holds byte n0-1, and no further.
+ *   Every present unit with len(u) > 0 is verified over its own bytes: chunks
+ *     c < ceil(len(u) / bytes_per_checksum), the last one over [c*bpc, len(u));
+ *     sums slots past that are not read.  Also in stripes with e == 0.
+ * HEC_CHECKSUM_NULL is HEC_ERR_INVALID_ARG: zero-padded slots through
+ * hec_scrub_device[_mixed] already give those results.  The other
+ * HEC_ERR_INVALID_ARG cases (nothing queued) are those of
+ * hec_scrub_crc_device[_mixed], plus data_len or a stripe_bytes entry out of
+ * range; every argument is checked before the coder's device is touched.
+ * Full stripes make exactly the launches of hec_scrub_crc_device[_mixed] (with
+ * data_len == 0 / stripe_bytes == NULL every result, flag byte and launch is
+ * theirs).  Short stripes run a one-pass kernel (k + e reads over [0, n0)) for
+ * k in {2,3,6,10}, 1 <= e <= 4, bytes_per_checksum == 512, 16-B aligned bases,
+ * strides and cell_len (below 2^31) and plans whose first row has no zero --
+ * the lengths themselves may be any byte count -- and a byte-wise kernel with
+ * the same results for every other shape and for groups with e == 0.
+ * Uniform form: the existing call over the first stripes-1 stripes, then one
+ * short-stripe launch with r passed by value; kernels only, capturable into a
+ * graph.  Mixed form: per distinct mask one launch over its full stripes and
+ * one over its short stripes.  Its workspace
+ * (hec_scrub_crc_rows_mixed_workspace_size, never smaller than
+ * hec_scrub_crc_mixed_workspace_size; required in full whenever a stripe is
+ * short and some stripe has a present unit) holds the short stripes' lists and
+ * their u64 lengths behind what hec_scrub_crc_device_mixed keeps there;
+ * alignment and lifetime rules are that call's. */
+int hec_scrub_crc_rows_device(hec_coder_t *coder, int checksum_type,
+                              const uint8_t *const *d_shards, const size_t *shard_strides,
+                              size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                              const uint8_t *d_expected, uint8_t *d_bad,
+                              hec_scrub_result_t *d_results, void *hip_stream);
+
+size_t hec_scrub_crc_rows_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+
+int hec_scrub_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
+                                    const uint8_t *const *d_shards, const size_t *shard_strides,
+                                    const uint64_t *present, const uint64_t *stripe_bytes,
+                                    size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                    const uint8_t *d_expected, uint8_t *d_bad,
+                                    hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
+                                    void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

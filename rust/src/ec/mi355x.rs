@@ -153,6 +153,17 @@ unsafe extern "C" {
                                   stripes: usize, bytes_per_checksum: usize, d_expected: *const u8,
                                   d_bad: *mut u8, d_results: *mut ScrubResult, d_workspace: *mut c_void,
                                   workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    fn hec_scrub_crc_rows_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                 shard_strides: *const usize, cell_len: usize, stripes: usize,
+                                 bytes_per_checksum: usize, data_len: u64, d_expected: *const u8, d_bad: *mut u8,
+                                 d_results: *mut ScrubResult, stream: *mut c_void) -> c_int;
+    fn hec_scrub_crc_rows_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_scrub_crc_rows_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                       shard_strides: *const usize, present: *const u64, stripe_bytes: *const u64,
+                                       cell_len: usize, stripes: usize, bytes_per_checksum: usize,
+                                       d_expected: *const u8, d_bad: *mut u8, d_results: *mut ScrubResult,
+                                       d_workspace: *mut c_void, workspace_bytes: usize,
+                                       stream: *mut c_void) -> c_int;
     fn hec_crc_concat(checksum_type: c_int, crc_a: u32, crc_b: u32, len_b: u64, out: *mut u32) -> c_int;
     fn hec_composite_crc(checksum_type: c_int, sums: *const u8, n_units: usize, data_units: usize, cell_len: usize,
                          stripes: usize, bytes_per_checksum: usize, data_len: u64, cell_crcs: *mut u8,
@@ -653,6 +664,59 @@ impl GpuCoder {
             hec_scrub_crc_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
                                        present.as_ptr(), cell, present.len(), bytes_per_checksum, expected, bad,
                                        results, workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// `scrub_crc_device` for a group whose last stripe is short
+    /// (`hec_scrub_crc_rows_device`).  `data_len` as for
+    /// `composite_crc_device` (0 = every stripe full): the last stripe is
+    /// checked over its positions below n0 = min(cell, r) with every unit zero
+    /// from its own length on, and every unit is verified over its own bytes;
+    /// no slot byte at or past a unit's length is looked at.
+    ///
+    /// # Safety
+    /// As `scrub_crc_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn scrub_crc_rows_device(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                        cell: usize, stripes: usize, bytes_per_checksum: usize, data_len: u64,
+                                        expected: *const u8, bad: *mut u8, results: *mut ScrubResult,
+                                        stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_crc_rows_device(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(), cell,
+                                      stripes, bytes_per_checksum, data_len, expected, bad, results, stream)
+        })
+    }
+
+    /// Device bytes `scrub_crc_rows_device_mixed` needs for `stripes` stripes.
+    pub fn scrub_crc_rows_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_scrub_crc_rows_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// `scrub_crc_device_mixed` with the logical bytes of every stripe
+    /// (`hec_scrub_crc_rows_device_mixed`): `stripe_bytes` (`None` = every
+    /// stripe full) has one entry per stripe, 0 or `k * cell` = that stripe is
+    /// full.  `workspace` is device memory of
+    /// `scrub_crc_rows_mixed_workspace_size(stripes)` bytes (16-byte aligned),
+    /// untouched until `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `scrub_crc_device_mixed`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn scrub_crc_rows_device_mixed(&self, checksum_type: i32, shards: &[*const u8],
+                                              shard_strides: &[usize], present: &[u64], stripe_bytes: Option<&[u64]>,
+                                              cell: usize, bytes_per_checksum: usize, expected: *const u8,
+                                              bad: *mut u8, results: *mut ScrubResult, workspace: *mut c_void,
+                                              workspace_bytes: usize, stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(stripe_bytes.map_or(true, |b| b.len() == present.len()), "one length per stripe");
+        check(unsafe {
+            hec_scrub_crc_rows_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
+                                            present.as_ptr(), stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()),
+                                            cell, present.len(), bytes_per_checksum, expected, bad, results,
+                                            workspace, workspace_bytes, stream)
         })
     }
 

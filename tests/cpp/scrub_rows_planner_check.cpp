@@ -1,0 +1,220 @@
+// scrub_rows_planner_check.cpp -- the host-side planning of
+// hec_scrub_crc_rows_device_mixed (hdfs-native_amd/csrc/ec_capi.cpp:
+// scrub_rows_groups, rows_lists, scrub_rows_layout, write_rows_image,
+// scrub_rows_workspace) against a restatement built straight from the masks
+// and lengths, in a stand-alone program under AddressSanitizer + UBSan.  The
+// library's translation unit is included, so the code checked is the code the
+// library compiles; only host-only coders (HEC_DEVICE_HOST) are created and no
+// HIP call is made.
+//
+// Per batch: every group's full and short stripe lists and the short stripes'
+// lengths are compared with the restatement, and the image is written into a
+// malloc'd buffer of exactly the advertised workspace bytes filled with 0xCD,
+// then read back through the documented layout.
+// Run by tests/test_scrub_crc_rows.py (CPU).
+#include "../../hdfs-native_amd/csrc/ec_capi.cpp"
+
+#include <cstdarg>
+#include <map>
+#include <random>
+
+namespace {
+
+[[noreturn]] void die(const char* fmt, ...) {
+    char msg[512];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(msg, sizeof(msg), fmt, ap);
+    va_end(ap);
+    std::printf("scrub_rows_planner_check: FAIL %s\n", msg);
+    std::fflush(stdout);
+    _exit(1);
+}
+
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+size_t g_batches = 0, g_short = 0, g_full = 0;
+
+// One batch: present masks and lengths (bytes_null: the array is NULL).
+void check_batch(hec_coder* c, const std::vector<uint64_t>& present, const std::vector<uint64_t>& bytes,
+                 bool bytes_null, size_t cell_len, const char* what) {
+    const size_t k = c->k, m = c->m, n = k + m, S = present.size();
+    const uint64_t all = (uint64_t(1) << n) - 1;
+    const uint64_t full_bytes = uint64_t(k) * cell_len;
+
+    // the restatement: the masks with more than k units in the order they
+    // first appear, then the other masks with a unit in the order they first
+    // appear; each with its full and its short stripes, ascending
+    struct RefGroup {
+        uint64_t mask;
+        bool checked;
+        std::vector<uint32_t> full, shrt;
+        std::vector<uint64_t> lens;
+    };
+    std::vector<RefGroup> ref;
+    for (int pass = 0; pass < 2; pass++) {
+        std::map<uint64_t, size_t> ids;
+        for (size_t s = 0; s < S; s++) {
+            const uint64_t mask = present[s] & all;
+            const bool checked = size_t(__builtin_popcountll(mask)) > k;
+            if (!mask || checked != (pass == 0)) continue;
+            auto it = ids.find(mask);
+            if (it == ids.end()) {
+                it = ids.emplace(mask, ref.size()).first;
+                ref.push_back(RefGroup{mask, checked, {}, {}, {}});
+            }
+            const uint64_t r = bytes_null ? 0 : bytes[s];
+            if (r != 0 && r != full_bytes) {
+                ref[it->second].shrt.push_back(uint32_t(s));
+                ref[it->second].lens.push_back(r);
+            } else {
+                ref[it->second].full.push_back(uint32_t(s));
+            }
+        }
+    }
+    size_t n_full = 0, n_short = 0;
+    for (const RefGroup& g : ref) n_full += g.full.size(), n_short += g.shrt.size();
+
+    // the library, called as hec_scrub_crc_rows_device_mixed calls it
+    Batch b;
+    bool fits = true;
+    const int rc = scrub_rows_groups(c, present.data(), S, &b, &fits);
+    if (rc != HEC_OK) die("%s: scrub_rows_groups status %d", what, rc);
+    if (b.plans.size() != ref.size()) die("%s: %zu groups, restatement %zu", what, b.plans.size(), ref.size());
+    for (size_t p = 0; p < ref.size(); p++) {
+        const size_t e = ref[p].checked ? size_t(__builtin_popcountll(ref[p].mask)) - k : 0;  // extras; none: sums only
+        if (b.plans[p].rows.size() != e) die("%s: group %zu has %zu rows, restatement %zu", what, p, b.plans[p].rows.size(), e);
+        if ((all & ~b.plans[p].missing) != ref[p].mask) die("%s: group %zu's mask differs", what, p);
+    }
+    RowsLists l;
+    rows_lists(b, bytes_null ? nullptr : bytes.data(), k, cell_len, &l);
+    if (l.full.size() != n_full || l.shrt.size() != n_short || l.short_bytes.size() != n_short ||
+        l.full_off.size() != ref.size() + 1 || l.short_off.size() != ref.size() + 1)
+        die("%s: %zu full, %zu short entries; restatement %zu, %zu", what, l.full.size(), l.shrt.size(), n_full, n_short);
+    for (size_t p = 0; p < ref.size(); p++) {
+        const size_t f0 = l.full_off[p], f1 = l.full_off[p + 1], s0 = l.short_off[p], s1 = l.short_off[p + 1];
+        if (f1 - f0 != ref[p].full.size() || s1 - s0 != ref[p].shrt.size() || f1 > n_full || s1 > n_short)
+            die("%s: group %zu has %zu full and %zu short stripes, restatement %zu and %zu", what, p, f1 - f0, s1 - s0,
+                ref[p].full.size(), ref[p].shrt.size());
+    }
+
+    // the image, in a buffer of exactly the advertised size
+    const size_t advertised = hec_scrub_crc_rows_mixed_workspace_size(c, S);
+    const size_t base_ws = hec_scrub_crc_mixed_workspace_size(c, S);
+    if (advertised < base_ws) die("%s: workspace %zu below the full-stripe call's %zu", what, advertised, base_ws);
+    const RowsLayout w = scrub_rows_layout(k, m, S, n_full, n_short);
+    // the documented layout, restated
+    const size_t full_pos = up256(hec_scrub_mixed_workspace_size(c, S));
+    const size_t short_pos = up256(base_ws), bytes_pos = short_pos + up256(n_short * 4);
+    const size_t need = n_short ? bytes_pos + n_short * 8 : full_pos + n_full * 4;
+    if (w.full_pos != full_pos || w.short_pos != short_pos || w.bytes_pos != bytes_pos || w.need != need ||
+        w.image_bytes != need - full_pos)
+        die("%s: layout (%zu %zu %zu %zu), restatement (%zu %zu %zu %zu)", what, w.full_pos, w.short_pos, w.bytes_pos,
+            w.need, full_pos, short_pos, bytes_pos, need);
+    if (need > advertised) die("%s: image needs %zu of %zu advertised bytes", what, need, advertised);
+    if (full_pos + n_full * 4 > short_pos) die("%s: the full lists run into the short ones", what);
+    uint8_t* buf = static_cast<uint8_t*>(std::malloc(advertised));
+    std::memset(buf, 0xCD, advertised);
+    write_rows_image(buf + w.full_pos, l, w);
+    for (size_t i = 0; i < full_pos; i++)
+        if (buf[i] != 0xCD) die("%s: byte %zu before the image was written", what, i);
+    for (size_t i = need; i < advertised; i++)
+        if (buf[i] != 0xCD) die("%s: byte %zu behind the image was written", what, i);
+    for (size_t i = full_pos; i < need; i++) {
+        const bool in_full = i < full_pos + n_full * 4;
+        const bool in_short = n_short && i >= short_pos && i < short_pos + n_short * 4;
+        const bool in_bytes = n_short && i >= bytes_pos;
+        if (!in_full && !in_short && !in_bytes && buf[i] != 0) die("%s: pad byte %zu is %#x", what, i, buf[i]);
+    }
+    size_t fat = 0, sat = 0;
+    for (size_t p = 0; p < ref.size(); p++) {
+        if (!ref[p].full.empty() && std::memcmp(buf + full_pos + fat * 4, ref[p].full.data(), ref[p].full.size() * 4) != 0)
+            die("%s: group %zu's full stripes differ", what, p);
+        if (!ref[p].shrt.empty()) {
+            if (std::memcmp(buf + short_pos + sat * 4, ref[p].shrt.data(), ref[p].shrt.size() * 4) != 0)
+                die("%s: group %zu's short stripes differ", what, p);
+            if (std::memcmp(buf + bytes_pos + sat * 8, ref[p].lens.data(), ref[p].lens.size() * 8) != 0)
+                die("%s: group %zu's lengths differ", what, p);
+        }
+        if (fat != l.full_off[p] || sat != l.short_off[p]) die("%s: group %zu's offsets differ", what, p);
+        fat += ref[p].full.size();
+        sat += ref[p].shrt.size();
+    }
+    std::free(buf);
+    g_batches++;
+    g_short += n_short;
+    g_full += n_full;
+}
+
+void check_shape(size_t k, size_t m) {
+    hec_coder_t* c = nullptr;
+    if (hec_coder_create(k, m, HEC_DEVICE_HOST, &c) != HEC_OK || !c) die("hec_coder_create(%zu, %zu)", k, m);
+    const size_t n = k + m, cell_len = 9232;
+    const uint64_t all = (uint64_t(1) << n) - 1, full_bytes = uint64_t(k) * cell_len;
+    std::mt19937_64 rng(2000 * k + m);
+    // nothing lost, every single-loss mask, and a seeded sample of multi-loss
+    // masks: up to m lost (e == 0) and more than m lost (fewer than k units)
+    std::vector<uint64_t> masks{all};
+    for (size_t u = 0; u < n; u++) masks.push_back(all & ~(uint64_t(1) << u));
+    for (int i = 0; i < 24; i++) {
+        uint64_t mask = all;
+        const size_t lose = 2 + rng() % (m + 1);
+        while (size_t(__builtin_popcountll(all & ~mask)) < lose) mask &= ~(uint64_t(1) << (rng() % n));
+        masks.push_back(mask);
+    }
+    masks.push_back(0);  // a stripe without a unit
+    const uint64_t fixed[] = {0, full_bytes, 1, cell_len, cell_len + 1};
+    size_t last = 0;
+    for (size_t S : {size_t(1), size_t(7), size_t(1000)}) {
+        const size_t adv = hec_scrub_crc_rows_mixed_workspace_size(c, S);
+        if (adv < last) die("workspace size shrinks at %zu stripes", S);
+        last = adv;
+        for (int variant = 0; variant < 6; variant++) {
+            std::vector<uint64_t> present(S), bytes(S);
+            for (size_t s = 0; s < S; s++) {
+                present[s] = masks[(variant < 2 ? 1 + (s + variant) % n : rng() % masks.size())];
+                if (variant == 5) present[s] |= ~all;  // bits above k+m are ignored
+                const uint64_t pick = rng() % 8;
+                bytes[s] = variant == 1 ? 0 : pick < 5 ? fixed[pick] : 1 + rng() % full_bytes;
+                if (variant == 2) bytes[s] = 1 + rng() % (full_bytes - 1);  // every stripe short
+            }
+            char what[96];
+            std::snprintf(what, sizeof(what), "RS(%zu,%zu) S=%zu variant %d", k, m, S, variant);
+            check_batch(c, present, bytes, variant == 0, cell_len, what);
+        }
+    }
+    // lengths above k * cell_len, HEC_CHECKSUM_NULL and a data_len out of range
+    // are refused before the coder's device is looked at
+    {
+        uint64_t present = all & ~uint64_t(1), bytes = full_bytes + 1;
+        int rc = hec_scrub_crc_rows_device_mixed(c, HEC_CHECKSUM_CRC32C, nullptr, nullptr, &present, &bytes, cell_len, 1,
+                                                 512, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        if (rc != HEC_ERR_INVALID_ARG) die("stripe_bytes above k * cell_len: status %d", rc);
+        bytes = ~uint64_t(0);
+        rc = hec_scrub_crc_rows_device_mixed(c, HEC_CHECKSUM_CRC32C, nullptr, nullptr, &present, &bytes, cell_len, 1,
+                                             512, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+        if (rc != HEC_ERR_INVALID_ARG) die("stripe_bytes of 2^64 - 1: status %d", rc);
+        rc = hec_scrub_crc_rows_device(c, HEC_CHECKSUM_NULL, nullptr, nullptr, cell_len, 1, 512, 0, nullptr, nullptr,
+                                       nullptr, nullptr);
+        if (rc != HEC_ERR_INVALID_ARG) die("HEC_CHECKSUM_NULL: status %d", rc);
+        rc = hec_scrub_crc_rows_device(c, HEC_CHECKSUM_CRC32C, nullptr, nullptr, cell_len, 2, 512, full_bytes, nullptr,
+                                       nullptr, nullptr, nullptr);
+        if (rc != HEC_ERR_INVALID_ARG) die("data_len inside the last stripe but one: status %d", rc);
+        rc = hec_scrub_crc_rows_device(c, HEC_CHECKSUM_CRC32C, nullptr, nullptr, cell_len, 2, 512, full_bytes + 1,
+                                       nullptr, nullptr, nullptr, nullptr);
+        if (rc != HEC_ERR_DEVICE) die("a valid call on a host-only coder: status %d", rc);
+    }
+    hec_coder_destroy(c);
+}
+
+}  // namespace
+
+int main() {
+    check_shape(3, 2);
+    check_shape(6, 3);
+    check_shape(10, 4);
+    check_shape(12, 6);
+    std::printf("scrub_rows_planner_check: ok, %zu batches, %zu full and %zu short list entries\n", g_batches, g_full,
+                g_short);
+    return 0;
+}
