@@ -36,6 +36,7 @@
 #include "checksum.hpp"
 #include "checksum_tables.hpp"
 #include "crc_compose.hpp"
+#include "ec_encode_rows.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
 #include "ec_reconstruct_rows.hpp"
@@ -3948,6 +3949,237 @@ int hec_scrub_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uin
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
+    });
+}
+
+// ---- encode with chunk sums of short stripes ----------------------------------
+// hec_encode_crc_rows_device*: hec_encode_crc_device with a checksum type and
+// the lengths of hec_reconstruct_crc_rows_device* -- a stripe of r < k *
+// cell_len logical bytes gets its parity over [0, n0) and every unit the sums
+// of its own bytes (ec_encode_rows.hip).  Full CRC32C stripes run as
+// hec_encode_crc_device runs them, launch for launch.
+
+}  // extern "C"
+
+namespace {
+
+// [the stripes' logical bytes: u64 x stripes], 0 rewritten to k * cell_len.
+size_t encode_rows_workspace(size_t stripes) { return stripes * sizeof(uint64_t); }
+
+// The lengths image of hec_encode_crc_rows_device_mixed: one u64 per stripe.
+// Returns the bytes written.  Host only.
+size_t write_encode_rows_image(uint8_t* host, const uint64_t* stripe_bytes, size_t stripes, size_t k,
+                               size_t cell_len) {
+    const uint64_t full = uint64_t(k) * cell_len;
+    for (size_t s = 0; s < stripes; s++) {
+        const uint64_t r = stripe_bytes[s] == 0 ? full : stripe_bytes[s];
+        std::memcpy(host + s * sizeof(uint64_t), &r, sizeof(r));
+    }
+    return stripes * sizeof(uint64_t);
+}
+
+// The buffers of both entry points.
+int encode_rows_buffers_check(const hec_coder* c, const uint8_t* const* d_data, const size_t* data_strides,
+                              uint8_t* const* d_parity, const size_t* parity_strides, const uint8_t* d_sums) {
+    if (!d_data || !data_strides || !d_parity || !parity_strides || !d_sums ||
+        (reinterpret_cast<uintptr_t>(d_sums) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k; i++)
+        if (!d_data[i]) return HEC_ERR_INVALID_ARG;
+    for (size_t j = 0; j < c->m; j++)
+        if (!d_parity[j]) return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// `stripes` stripes from batch stripe lens.stripe0 on, lengths in `lens`:
+// gf_encode_crc_rows where the launcher takes the shape, else
+// gf_encode_rows_bytes, four parity rows per launch, the first launch summing
+// the data units.  The caller has checked the buffers.
+int encode_rows_launch(hec_coder* c, int kind, const hec::ReconRowsLens& lens, const uint8_t* const* d_data,
+                       const size_t* data_strides, uint8_t* const* d_parity, const size_t* parity_strides,
+                       size_t cell_len, size_t stripes, size_t bpc, uint8_t* d_sums, hipStream_t stream) {
+    if (stripes == 0) return HEC_OK;
+    const size_t k = c->k, m = c->m;
+    if (bpc == 512 && m <= size_t(hec::kMaxR)) {
+        hec::MatmulArgs a;
+        std::memset(&a, 0, sizeof(a));
+        for (size_t i = 0; i < k; i++) {
+            a.in[i] = d_data[i];
+            a.in_stride[i] = data_strides[i];
+        }
+        for (size_t j = 0; j < m; j++) {
+            a.out[j] = d_parity[j];
+            a.out_stride[j] = parity_strides[j];
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = c->enc[(k + j) * k + i];
+        }
+        a.k = int32_t(k);
+        a.r = int32_t(m);
+        a.cell_len = cell_len;
+        a.stripes = stripes;
+        hec::EncodeRowsCrcArgs cs;
+        std::memset(&cs, 0, sizeof(cs));
+        cs.sums = d_sums;
+        cs.n_total = uint32_t(k + m);
+        cs.kind = kind;
+        const int rc = hec::launch_encode_crc_rows(a, cs, lens, c->device, stream);
+        if (rc == 0) return HEC_OK;
+        if (rc > 0) return to_status(rc);
+        // -1: refused, nothing launched
+    }
+    hec::EncodeRowsBytesArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t i = 0; i < k; i++) {
+        a.in[i] = d_data[i];
+        a.in_stride[i] = data_strides[i];
+    }
+    a.k = int32_t(k);
+    a.n_total = uint32_t(k + m);
+    a.sums = d_sums;
+    a.kind = kind;
+    a.stripes = stripes;
+    a.lens = lens;
+    a.cell_len = cell_len;
+    a.bytes_per_checksum = bpc;
+    a.data_sums = 1;
+    for (size_t j0 = 0; j0 < m; j0 += size_t(hec::kMaxR)) {
+        const size_t rn = std::min(size_t(hec::kMaxR), m - j0);
+        std::memset(a.coef, 0, sizeof(a.coef));
+        for (size_t j = 0; j < rn; j++) {
+            a.out[j] = d_parity[j0 + j];
+            a.out_stride[j] = parity_strides[j0 + j];
+            a.out_id[j] = uint8_t(k + j0 + j);
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = c->enc[(k + j0 + j) * k + i];
+        }
+        a.r = int32_t(rn);
+        const int rc = hec::launch_encode_rows_bytes(a, c->device, stream);
+        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+        a.data_sums = 0;  // the data units are summed once
+    }
+    return HEC_OK;
+}
+
+// `stripes` full stripes from stripe 0 on.  CRC32C: hec_encode_crc_device.
+// CRC32: gf_encode_crc_rows with every stripe at k * cell_len where it takes
+// the shape, else hec_encode_device, then hec_checksum_device.
+int encode_rows_full(hec_coder* c, int checksum_type, int kind, const uint8_t* const* d_data,
+                     const size_t* data_strides, uint8_t* const* d_parity, const size_t* parity_strides,
+                     size_t cell_len, size_t stripes, size_t bpc, uint8_t* d_sums, void* hip_stream) {
+    if (stripes == 0) return HEC_OK;
+    if (kind == hec::crc::kCrc32c)
+        return hec_encode_crc_device(c, d_data, data_strides, d_parity, parity_strides, cell_len, stripes, bpc, d_sums,
+                                     hip_stream);
+    const size_t k = c->k, m = c->m;
+    bool one_pass = bpc == 512 && m <= size_t(hec::kMaxR) && cell_len % 16 == 0 && cell_len <= 0x7FFFFFFFull &&
+                    stripes <= 0xFFFFFFFFull && (k == 2 || k == 3 || k == 6 || k == 10);
+    for (size_t i = 0; i < k; i++)
+        one_pass = one_pass && ((reinterpret_cast<uintptr_t>(d_data[i]) | data_strides[i]) & 15u) == 0;
+    for (size_t j = 0; j < m; j++)
+        one_pass = one_pass && ((reinterpret_cast<uintptr_t>(d_parity[j]) | parity_strides[j]) & 15u) == 0;
+    if (one_pass) {
+        const int rc = guarded([&]() -> int {
+            DeviceGuard g(c->device);
+            if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+            return encode_rows_launch(c, kind, hec::ReconRowsLens{nullptr, uint64_t(k) * cell_len, 0}, d_data,
+                                      data_strides, d_parity, parity_strides, cell_len, stripes, bpc, d_sums,
+                                      static_cast<hipStream_t>(hip_stream));
+        });
+        return rc;
+    }
+    const int rc = hec_encode_device(c, d_data, data_strides, d_parity, parity_strides, cell_len, stripes, hip_stream);
+    if (rc != HEC_OK) return rc;
+    const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t st[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    for (size_t i = 0; i < k; i++) {
+        bases[i] = d_data[i];
+        st[i] = data_strides[i];
+    }
+    for (size_t j = 0; j < m; j++) {
+        bases[k + j] = d_parity[j];
+        st[k + j] = parity_strides[j];
+    }
+    return hec_checksum_device(c, checksum_type, bases, st, k + m, cell_len, stripes, bpc, d_sums, hip_stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_encode_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_data,
+                               const size_t* data_strides, uint8_t* const* d_parity, const size_t* parity_strides,
+                               size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                               uint8_t* d_sums, void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    hec::crc::Geometry geo;
+    if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
+        return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_encode_crc_rows_device");
+    chk = encode_rows_buffers_check(c, d_data, data_strides, d_parity, parity_strides, d_sums);
+    if (chk != HEC_OK) return chk;
+    if (stripes == 0) return HEC_OK;
+    // every stripe full: one call over all of them
+    if (geo.last_len == uint64_t(c->k) * cell_len)
+        return encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
+                                stripes, bytes_per_checksum, d_sums, hip_stream);
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    // the stripes - 1 full stripes, then one launch over the last
+    const int rc = encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
+                                    stripes - 1, bytes_per_checksum, d_sums, hip_stream);
+    if (rc != HEC_OK) return rc;
+    return guarded([&]() -> int {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        return encode_rows_launch(c, kind, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, d_data, data_strides,
+                                  d_parity, parity_strides, cell_len, 1, bytes_per_checksum, d_sums,
+                                  static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+size_t hec_encode_crc_rows_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c) return 0;
+    return encode_rows_workspace(stripes);
+}
+
+int hec_encode_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_data,
+                                     const size_t* data_strides, uint8_t* const* d_parity,
+                                     const size_t* parity_strides, const uint64_t* stripe_bytes, size_t cell_len,
+                                     size_t stripes, size_t bytes_per_checksum, uint8_t* d_sums, void* d_workspace,
+                                     size_t workspace_bytes, void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    if (stripes > SIZE_MAX / sizeof(uint64_t)) return HEC_ERR_INVALID_ARG;
+    bool any_short = false;
+    for (size_t s = 0; stripe_bytes && s < stripes; s++) {
+        if (stripe_bytes[s] > uint64_t(c->k) * cell_len) return HEC_ERR_INVALID_ARG;
+        any_short = any_short || rows_short(stripe_bytes[s], c->k, cell_len);
+    }
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_encode_crc_rows_device_mixed");
+    chk = encode_rows_buffers_check(c, d_data, data_strides, d_parity, parity_strides, d_sums);
+    if (chk != HEC_OK) return chk;
+    if (any_short && (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 7u) ||
+                      workspace_bytes < encode_rows_workspace(stripes)))
+        return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    // no short entry: the uniform form with data_len == 0
+    if (!any_short)
+        return encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
+                                stripes, bytes_per_checksum, d_sums, hip_stream);
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    // one launch over all stripes, full ones included, with the lengths on
+    // the device
+    return guarded([&]() -> int {
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const int rc = upload_pinned(c, encode_rows_workspace(stripes), d_workspace, stream, [&](uint8_t* host) {
+            write_encode_rows_image(host, stripe_bytes, stripes, c->k, cell_len);
+        });
+        if (rc != HEC_OK) return rc;
+        return encode_rows_launch(c, kind, hec::ReconRowsLens{static_cast<const uint64_t*>(d_workspace), 0, 0}, d_data,
+                                  data_strides, d_parity, parity_strides, cell_len, stripes, bytes_per_checksum,
+                                  d_sums, stream);
     });
 }
 

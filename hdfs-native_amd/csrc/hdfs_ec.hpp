@@ -341,6 +341,48 @@ class Coder {
                                               workspace_bytes, hip_stream));
     }
 
+    // Parity and chunk sums of a group whose last stripe is short
+    // (hec_encode_crc_rows_device): encode + sums with a checksum type and
+    // data_len as for composite_crc_device (0 = every stripe full); the last
+    // stripe's parity units get their n0 bytes, nothing behind them is
+    // written, and every unit gets the sums of its own bytes.
+    void encode_crc_rows_device(int checksum_type, const std::vector<const uint8_t*>& d_data,
+                                const std::vector<size_t>& data_strides, const std::vector<uint8_t*>& d_parity,
+                                const std::vector<size_t>& parity_strides, size_t cell_len, size_t stripes,
+                                size_t bytes_per_checksum, uint64_t data_len, uint8_t* d_sums,
+                                void* hip_stream = nullptr) const {
+        if (d_data.size() != k_ || data_strides.size() != k_ || d_parity.size() != m_ || parity_strides.size() != m_)
+            throw std::invalid_argument("encode_crc_rows_device: need data_units data and parity_units parity units");
+        check(hec_encode_crc_rows_device(h_.get(), checksum_type, d_data.data(), data_strides.data(), d_parity.data(),
+                                         parity_strides.data(), cell_len, stripes, bytes_per_checksum, data_len,
+                                         d_sums, hip_stream));
+    }
+    // One length per stripe (hec_encode_crc_rows_device_mixed): stripe_bytes
+    // (nullptr = every stripe full) holds `stripes` entries, 0 or k * cell_len
+    // = that stripe is full; d_workspace of
+    // encode_crc_rows_mixed_workspace_size(stripes) bytes, 8-byte aligned,
+    // needed only when a stripe is short, untouched until the stream has
+    // passed the call.
+    size_t encode_crc_rows_mixed_workspace_size(size_t stripes) const {
+        return hec_encode_crc_rows_mixed_workspace_size(h_.get(), stripes);
+    }
+    void encode_crc_rows_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_data,
+                                      const std::vector<size_t>& data_strides, const std::vector<uint8_t*>& d_parity,
+                                      const std::vector<size_t>& parity_strides,
+                                      const std::vector<uint64_t>* stripe_bytes, size_t cell_len, size_t stripes,
+                                      size_t bytes_per_checksum, uint8_t* d_sums, void* d_workspace,
+                                      size_t workspace_bytes, void* hip_stream = nullptr) const {
+        if (d_data.size() != k_ || data_strides.size() != k_ || d_parity.size() != m_ || parity_strides.size() != m_)
+            throw std::invalid_argument(
+                "encode_crc_rows_device_mixed: need data_units data and parity_units parity units");
+        if (stripe_bytes && stripe_bytes->size() != stripes)
+            throw std::invalid_argument("encode_crc_rows_device_mixed: one length per stripe");
+        check(hec_encode_crc_rows_device_mixed(h_.get(), checksum_type, d_data.data(), data_strides.data(),
+                                               d_parity.data(), parity_strides.data(),
+                                               stripe_bytes ? stripe_bytes->data() : nullptr, cell_len, stripes,
+                                               bytes_per_checksum, d_sums, d_workspace, workspace_bytes, hip_stream));
+    }
+
     // Verified reconstruction of a device-resident batch, asynchronous on
     // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
     // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and

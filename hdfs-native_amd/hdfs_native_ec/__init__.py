@@ -72,6 +72,7 @@ EXPORTS = [
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
     "hec_scrub_crc_rows_device", "hec_scrub_crc_rows_mixed_workspace_size", "hec_scrub_crc_rows_device_mixed",
+    "hec_encode_crc_rows_device", "hec_encode_crc_rows_mixed_workspace_size", "hec_encode_crc_rows_device_mixed",
     "hec_crc_concat", "hec_composite_crc", "hec_composite_crc_workspace_size", "hec_composite_crc_device",
 ]
 
@@ -217,6 +218,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_crc_rows_mixed_workspace_size": ([P, S], S),
         "hec_scrub_crc_rows_device_mixed": ([P, I, PP, SP, ctypes.POINTER(ctypes.c_uint64),
                                              ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, P, S, P], I),
+        "hec_encode_crc_rows_device": ([P, I, PP, SP, PP, SP, S, S, S, ctypes.c_uint64, P, P], I),
+        "hec_encode_crc_rows_mixed_workspace_size": ([P, S], S),
+        "hec_encode_crc_rows_device_mixed": ([P, I, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, S,
+                                              P], I),
         "hec_crc_concat": ([I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)], I),
         "hec_composite_crc": ([I, P, S, S, S, S, S, ctypes.c_uint64, P, P, P], I),
         "hec_composite_crc_workspace_size": ([S, S], S),
@@ -788,6 +793,38 @@ class Coder:
                                          _sp(parity_strides), cell_len, stripes, bytes_per_checksum,
                                          ctypes.c_void_p(sums_ptr), ctypes.c_void_p(stream)))
 
+    def encode_crc_rows_device(self, data_ptrs, data_strides, parity_ptrs, parity_strides, cell_len, stripes,
+                               sums_ptr, data_len: int = 0, bytes_per_checksum: int = 512,
+                               checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_encode_crc_rows_device: encode_crc_device with a checksum type
+        for a group whose last stripe is short.  data_len as for composite_crc
+        (0 = every stripe full): the last stripe's parity units get their n0 =
+        min(cell, r) bytes, nothing at or past n0 is written, and every unit
+        gets the sums of its own bytes."""
+        _check(self._lib.hec_encode_crc_rows_device(
+            self._h, checksum_type, None if data_ptrs is None else _pp([p or 0 for p in data_ptrs]),
+            _sp(data_strides), None if parity_ptrs is None else _pp([p or 0 for p in parity_ptrs]),
+            _sp(parity_strides), cell_len, stripes, bytes_per_checksum, data_len, ctypes.c_void_p(sums_ptr),
+            ctypes.c_void_p(stream)))
+
+    def encode_crc_rows_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_encode_crc_rows_mixed_workspace_size(self._h, stripes)
+
+    def encode_crc_rows_device_mixed(self, data_ptrs, data_strides, parity_ptrs, parity_strides, stripe_bytes,
+                                     cell_len, stripes, sums_ptr, workspace_ptr, workspace_bytes,
+                                     bytes_per_checksum: int = 512, checksum_type: int = CHECKSUM_CRC32C,
+                                     stream: int = 0) -> None:
+        """hec_encode_crc_rows_device_mixed: the logical bytes of every stripe
+        (stripe_bytes[s]; None = all full; 0 or k * cell_len = that stripe is
+        full).  The workspace (encode_crc_rows_mixed_workspace_size(stripes)
+        bytes, 8-byte aligned) is needed only when a stripe is short."""
+        lens = None if stripe_bytes is None else (ctypes.c_uint64 * max(stripes, 1))(*stripe_bytes)
+        _check(self._lib.hec_encode_crc_rows_device_mixed(
+            self._h, checksum_type, None if data_ptrs is None else _pp([p or 0 for p in data_ptrs]),
+            _sp(data_strides), None if parity_ptrs is None else _pp([p or 0 for p in parity_ptrs]),
+            _sp(parity_strides), lens, cell_len, stripes, bytes_per_checksum, ctypes.c_void_p(sums_ptr),
+            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)))
+
     def decode_mixed_workspace_size(self, stripes: int) -> int:
         return self._lib.hec_decode_mixed_workspace_size(self._h, stripes)
 
@@ -1194,6 +1231,40 @@ def reconstruct_crc_rows_batch_mixed(coder: Coder, cells, present_masks: Sequenc
                                             bad_ptr=None if bad is None else bad.data_ptr(),
                                             bytes_per_checksum=bytes_per_checksum, checksum_type=checksum_type,
                                             stream=s.cuda_stream)
+    return workspace
+
+
+def encode_crc_rows_batch(coder: Coder, cells, sums, data_len: int = 0, stripe_bytes=None,
+                          checksum_type: int = CHECKSUM_CRC32C, bytes_per_checksum: int = 512, stream=None,
+                          workspace=None):
+    """Parity and chunk sums of a batch with short stripes: cells is a uint8
+    cuda tensor [S, k+m, width] (units 0 .. k-1 are read, k .. k+m-1 written),
+    sums the [S, k+m, nck] sums array.  With stripe_bytes (one entry per stripe;
+    0 or k * width = that stripe is full) the mixed form runs, else the uniform
+    form with data_len (0 = every stripe full).  A short stripe's parity units
+    get their n0 bytes and nothing behind, and every unit the sums of its own
+    bytes.  Returns the workspace the mixed form allocated or was given
+    (reusable once the stream has passed the call), or None."""
+    import torch
+    k, m = coder.data_units, coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, k + m)
+    if stripe_bytes is None:
+        coder.encode_crc_rows_device(ptrs[:k], strides[:k], ptrs[k:], strides[k:], cells.shape[2], S, sums.data_ptr(),
+                                     data_len=data_len, bytes_per_checksum=bytes_per_checksum,
+                                     checksum_type=checksum_type, stream=s.cuda_stream)
+        return None
+    if data_len:
+        raise ValueError("encode_crc_rows_batch: data_len or stripe_bytes, not both")
+    if workspace is None:
+        workspace = torch.empty(max(coder.encode_crc_rows_mixed_workspace_size(S), 8), dtype=torch.uint8,
+                                device=cells.device)
+        workspace.record_stream(s)
+    coder.encode_crc_rows_device_mixed(ptrs[:k], strides[:k], ptrs[k:], strides[k:], list(stripe_bytes),
+                                       cells.shape[2], S, sums.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                       bytes_per_checksum=bytes_per_checksum, checksum_type=checksum_type,
+                                       stream=s.cuda_stream)
     return workspace
 
 

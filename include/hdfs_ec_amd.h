@@ -797,6 +797,82 @@ int hec_scrub_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
                                     hec_scrub_result_t *d_results, void *d_workspace, size_t workspace_bytes,
                                     void *hip_stream);
 
+/* ---- Encode with chunk sums of short stripes ------------------------------ *
+ * The writer's side of the two families above (CellBuffer::encode feeding
+ * WritePacket::calculate_checksum): hec_encode_crc_device with a checksum type
+ * and with the geometry of hec_reconstruct_crc_rows_device[_mixed] /
+ * hec_scrub_crc_rows_device[_mixed] -- a stripe of r logical bytes, 1 <= r <=
+ * k*cell_len, n0 = min(cell_len, r), data unit u of len(u) = min(cell_len,
+ * max(0, r - u*cell_len)) bytes, every parity unit of n0 bytes; data_len
+ * (uniform form) with the meaning and the range check of hec_composite_crc;
+ * stripe_bytes[stripes] (mixed form, host array, NULL = every stripe full) with
+ * 0 or k*cell_len = full and an entry above k*cell_len HEC_ERR_INVALID_ARG.  A
+ * group whose last stripe is short, or a batch of small files, goes write ->
+ * scrub -> composite on one stream and one sums array
+ * (hec_encode_crc_rows_device* -> hec_scrub_crc_rows_device* ->
+ * hec_composite_crc_device), with no padding by the caller.
+ * d_data[k] / d_parity[m] and their strides as hec_encode_crc_device; d_sums is
+ * [stripe][k+m][nck] big-endian u32, nck = ceil(cell_len /
+ * bytes_per_checksum), data unit i at i and parity unit j at k + j.
+ * In a short stripe:
+ *   A data unit counts as zero from len(u) on: no slot byte at or past len(u)
+ *     influences any output.  A data unit of length 0 is not read at all and
+ *     none of its sums words is written.  Nothing at or past cell_len of a slot
+ *     is read; on the 16-B aligned route a read of a non-empty unit's slot may
+ *     reach the end of the 16-byte block that holds byte n0-1, and no further.
+ *     A file-order buffer (base d + i*cell_len, stride k*cell_len, as
+ *     hec_encode_rows_device takes it) is therefore usable directly, without a
+ *     workspace and without zero-padding: the allocation must cover whole rows,
+ *     the bytes past data_len may be anything.
+ *   Parity unit j gets its n0 computed bytes at [0, n0); no byte at or past n0
+ *     of a parity slot is written.  This is the rule of
+ *     hec_reconstruct_crc_rows_device, not that of hec_encode_rows_device, which
+ *     zeroes the rest of the row.
+ *   Sums of data unit u: chunks c < ceil(len(u) / bytes_per_checksum), the last
+ *     over [c*bpc, len(u)); of a parity unit: chunks c < ceil(n0 / bpc).  Sums
+ *     slots past these are not written.  These are the sums
+ *     hec_composite_crc*, hec_scrub_crc_rows_device* and
+ *     hec_reconstruct_crc_rows_device* (as d_expected) expect.
+ * checksum_type is HEC_CHECKSUM_CRC32C or HEC_CHECKSUM_CRC32, also on full
+ * stripes; HEC_CHECKSUM_NULL and unknown types are HEC_ERR_INVALID_ARG
+ * (hec_encode_rows_device is the call without sums).
+ * Checks, in this order, nothing queued on any error: coder, type, cell_len,
+ * bytes_per_checksum, data_len / stripe_bytes (HEC_ERR_INVALID_ARG); a
+ * host-only coder (HEC_ERR_DEVICE); NULL arrays or entries, d_sums NULL or not
+ * 4-byte aligned, the workspace (HEC_ERR_INVALID_ARG); stripes == 0 is HEC_OK.
+ * Uniform form: with data_len == 0 or a full last stripe and CRC32C the call
+ * is hec_encode_crc_device, launch for launch.  Otherwise the first stripes-1
+ * stripes run so (CRC32: the short-stripe kernel with every stripe at
+ * k*cell_len, or hec_encode_device + hec_checksum_device for shapes it does not
+ * take) and one more launch covers the last stripe with r passed by value;
+ * kernels only, capturable into a graph.
+ * Mixed form: without a short entry, the uniform form with data_len == 0.  With
+ * one, a single launch of the short-stripe kernel over all stripes, the full
+ * ones included (a big file with one short stripe is the uniform form's case).
+ * d_workspace (hec_encode_crc_rows_mixed_workspace_size: 8 bytes per stripe; 0
+ * for a NULL coder) is needed only then: NULL, not 8-byte aligned or too small
+ * is HEC_ERR_INVALID_ARG.  It receives the u64 lengths (0 rewritten to
+ * k*cell_len) in one asynchronous copy and must stay untouched until the
+ * stream has passed the call.
+ * The one-pass kernel (k reads + m writes over [0, n0)) takes k in {2,3,6,10},
+ * m <= 4, bytes_per_checksum == 512, 16-B aligned bases, strides and cell_len
+ * (below 2^31); every other shape takes a byte-wise kernel with the same
+ * results.  All codecs (rs, xor, rs-legacy). */
+int hec_encode_crc_rows_device(hec_coder_t *coder, int checksum_type,
+                               const uint8_t *const *d_data, const size_t *data_strides,
+                               uint8_t *const *d_parity, const size_t *parity_strides,
+                               size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                               uint8_t *d_sums, void *hip_stream);
+
+size_t hec_encode_crc_rows_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+
+int hec_encode_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
+                                     const uint8_t *const *d_data, const size_t *data_strides,
+                                     uint8_t *const *d_parity, const size_t *parity_strides,
+                                     const uint64_t *stripe_bytes, size_t cell_len, size_t stripes,
+                                     size_t bytes_per_checksum,
+                                     uint8_t *d_sums, void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

@@ -164,6 +164,18 @@ unsafe extern "C" {
                                        d_expected: *const u8, d_bad: *mut u8, d_results: *mut ScrubResult,
                                        d_workspace: *mut c_void, workspace_bytes: usize,
                                        stream: *mut c_void) -> c_int;
+    fn hec_encode_crc_rows_device(c: *mut HecCoder, checksum_type: c_int, d_data: *const *const u8,
+                                  data_strides: *const usize, d_parity: *const *mut u8,
+                                  parity_strides: *const usize, cell_len: usize, stripes: usize,
+                                  bytes_per_checksum: usize, data_len: u64, d_sums: *mut u8,
+                                  stream: *mut c_void) -> c_int;
+    fn hec_encode_crc_rows_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_encode_crc_rows_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_data: *const *const u8,
+                                        data_strides: *const usize, d_parity: *const *mut u8,
+                                        parity_strides: *const usize, stripe_bytes: *const u64, cell_len: usize,
+                                        stripes: usize, bytes_per_checksum: usize, d_sums: *mut u8,
+                                        d_workspace: *mut c_void, workspace_bytes: usize,
+                                        stream: *mut c_void) -> c_int;
     fn hec_crc_concat(checksum_type: c_int, crc_a: u32, crc_b: u32, len_b: u64, out: *mut u32) -> c_int;
     fn hec_composite_crc(checksum_type: c_int, sums: *const u8, n_units: usize, data_units: usize, cell_len: usize,
                          stripes: usize, bytes_per_checksum: usize, data_len: u64, cell_crcs: *mut u8,
@@ -717,6 +729,68 @@ impl GpuCoder {
                                             present.as_ptr(), stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()),
                                             cell, present.len(), bytes_per_checksum, expected, bad, results,
                                             workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// Parity and chunk sums of a group whose last stripe is short
+    /// (`hec_encode_crc_rows_device`): `CellBuffer::encode` feeding
+    /// `WritePacket::calculate_checksum` on the device.  `data_len` as for
+    /// `composite_crc_device` (0 = every stripe full): the last stripe's
+    /// parity units get their n0 = min(cell, r) bytes, nothing at or past n0
+    /// is written, every unit gets the sums of its own bytes, and no data byte
+    /// at or past a unit's length is looked at.
+    ///
+    /// # Safety
+    /// `data[i] + s * data_strides[i]` (k units) and `parity[j] + s *
+    /// parity_strides[j]` (m units) must be device memory of `cell` bytes for
+    /// every stripe, `sums` device memory of `stripes * (k + m) * nck * 4`
+    /// bytes, all valid until `stream` has passed the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn encode_crc_rows_device(&self, checksum_type: i32, data: &[*const u8], data_strides: &[usize],
+                                         parity: &[*mut u8], parity_strides: &[usize], cell: usize, stripes: usize,
+                                         bytes_per_checksum: usize, data_len: u64, sums: *mut u8,
+                                         stream: *mut c_void) -> Result<()> {
+        assert!(data.len() == self.data_units && data_strides.len() == self.data_units, "one slot per data unit");
+        assert!(parity.len() == self.parity_units && parity_strides.len() == self.parity_units,
+                "one slot per parity unit");
+        check(unsafe {
+            hec_encode_crc_rows_device(self.raw, checksum_type as c_int, data.as_ptr(), data_strides.as_ptr(),
+                                       parity.as_ptr(), parity_strides.as_ptr(), cell, stripes, bytes_per_checksum,
+                                       data_len, sums, stream)
+        })
+    }
+
+    /// Device bytes `encode_crc_rows_device_mixed` needs for `stripes` stripes.
+    pub fn encode_crc_rows_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_encode_crc_rows_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// `encode_crc_rows_device` with the logical bytes of every stripe
+    /// (`hec_encode_crc_rows_device_mixed`): `stripe_bytes` (`None` = every
+    /// stripe full) has one entry per stripe, 0 or `k * cell` = that stripe is
+    /// full.  `workspace` is device memory of
+    /// `encode_crc_rows_mixed_workspace_size(stripes)` bytes (8-byte aligned),
+    /// needed only when a stripe is short and untouched until `stream` has
+    /// passed the call.
+    ///
+    /// # Safety
+    /// As `encode_crc_rows_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn encode_crc_rows_device_mixed(&self, checksum_type: i32, data: &[*const u8],
+                                               data_strides: &[usize], parity: &[*mut u8],
+                                               parity_strides: &[usize], stripe_bytes: Option<&[u64]>, cell: usize,
+                                               stripes: usize, bytes_per_checksum: usize, sums: *mut u8,
+                                               workspace: *mut c_void, workspace_bytes: usize,
+                                               stream: *mut c_void) -> Result<()> {
+        assert!(data.len() == self.data_units && data_strides.len() == self.data_units, "one slot per data unit");
+        assert!(parity.len() == self.parity_units && parity_strides.len() == self.parity_units,
+                "one slot per parity unit");
+        assert!(stripe_bytes.map_or(true, |b| b.len() == stripes), "one length per stripe");
+        check(unsafe {
+            hec_encode_crc_rows_device_mixed(self.raw, checksum_type as c_int, data.as_ptr(), data_strides.as_ptr(),
+                                             parity.as_ptr(), parity_strides.as_ptr(),
+                                             stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()), cell, stripes,
+                                             bytes_per_checksum, sums, workspace, workspace_bytes, stream)
         })
     }
 
