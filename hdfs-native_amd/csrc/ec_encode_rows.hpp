@@ -13,7 +13,7 @@
 
 namespace hec {
 
-// Checksum side of gf_encode_crc_rows.  The coding side is a MatmulArgs: in[]
+// Checksum side of gf_crc_rows<RowsEncode>.  The coding side is a MatmulArgs: in[]
 // = the k data units, out[] = the a.r parity units, coef = their rows of the
 // encode matrix.
 struct EncodeRowsCrcArgs {
@@ -22,7 +22,7 @@ struct EncodeRowsCrcArgs {
     int32_t kind;      // crc::Kind
 };
 
-// gf_encode_crc_rows: the data units count as zero from their length on and
+// gf_crc_rows<RowsEncode>: the data units count as zero from their length on and
 // none of their slot bytes at or past it influences an output; an empty data
 // unit is not read.  Parity j gets its n0 computed bytes at [0, n0), nothing
 // at or past n0 is written; every unit's sums are those of its own bytes,

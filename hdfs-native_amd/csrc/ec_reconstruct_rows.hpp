@@ -22,7 +22,7 @@ struct ReconRowsLens {
     uint64_t stripe0;              // without a stripe list, launch stripe s is batch stripe stripe0 + s
 };
 
-// gf_reconstruct_crc_rows: launch_reconstruct_crc for short stripes.  The
+// gf_crc_rows<RowsRepair>: launch_reconstruct_crc for short stripes.  The
 // survivors count as zero from their length on and are verified over their
 // own bytes; a target gets its computed bytes, zeros up to n0, and the sums
 // of its own bytes; nothing at or past n0 is written.  a.in / a.out /

@@ -11,21 +11,16 @@
 // kernels (ec_scrub_crc.hip, ec_scrub_mixed.hip) keep their machine code.
 //
 // gf_scrub_crc_rows is gf_scrub_crc (ec_scrub_crc.hip) with the length
-// handling of gf_reconstruct_crc_rows (ec_reconstruct_rows.hip): same tiles,
-// 16-B loads, GF step, checksum rounds (crc_stage.hpp) and locate tail, one
-// pass of k + e reads over [0, n0).
-//   - Tiles at or past n0 are skipped per wave (wave-uniform: n0 is a scalar).
-//   - A unit whose length ends at or before the wave's first byte is neither
-//     multiplied nor staged nor summed and no byte of its slot is read; a
-//     round whose units all ended is skipped.
-//   - Every unit still issues its SLABS loads (exact waits); those of an ended
-//     unit go to offset 0 of extra 0, which is a parity unit and so holds n0
-//     bytes.  Bytes at or past a unit's length are masked to zero in registers
-//     before the GF step and before they are staged, in the wave that holds
-//     the unit's end only.
-//   - A checksum round takes the length of the unit in the lane's round slot
-//     where gf_scrub_crc takes cell_len.
+// handling of gf_crc_rows, by the rules written in ec_rows_kernel.hpp: same
+// tiles, 16-B loads, GF step, checksum rounds (crc_stage.hpp) and locate
+// tail, one pass of k + e reads over [0, n0).  Its own:
+//   - The unit loop runs over k + e units; an extra is XORed into its row.
+//   - An ended unit's loads go to offset 0 of extra 0, which is a parity unit
+//     and so holds n0 bytes.
+//   - Every unit is staged and verified, every round compares.
 //   - The locate tail masks lanes at or past n0 out of the findings.
+// The kernel keeps the text of its tile preamble (lengths, cut, load_in,
+// product step, verify round): see profiles/rows_parts/README.md.
 //
 // gf_scrub_rows_bytes is the byte-wise route for every other shape, in the
 // style of gf_scrub_mixed_bytes plus gf_reconstruct_rows_bytes' verify lanes.
@@ -35,48 +30,10 @@
 #include <type_traits>
 #include <utility>
 
+#include "ec_rows_kernel.hpp"
 #include "ec_scrub_rows.hpp"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#include "crc_stage.hpp"
-#include "ec_fused_kernel.hpp"
-#pragma clang diagnostic pop
-#include "launch_parts.hpp"
 
 namespace hec {
-
-namespace {
-
-// Bytes of unit `uid` in a stripe of r logical bytes (n0 = min(cell_len, r)).
-__device__ __forceinline__ uint64_t rows_unit_len(uint32_t uid, uint32_t data_units, uint64_t r, uint64_t n0,
-                                                  uint64_t cell_len) {
-    if (uid >= data_units) return n0;
-    const uint64_t before = uint64_t(uid) * cell_len;
-    if (r <= before) return 0;
-    const uint64_t left = r - before;
-    return left < cell_len ? left : cell_len;
-}
-
-// The first `valid` bytes of a 16-B block (memory order), the rest zero.
-__device__ __forceinline__ u32x4 keep_bytes(u32x4 v, int32_t valid) {
-#pragma unroll
-    for (int d = 0; d < 4; d++) {
-        const int32_t vb = valid - 4 * d;
-        const uint32_t m = vb >= 4 ? 0xFFFFFFFFu : (vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u));
-        v[d] &= m;
-    }
-    return v;
-}
-
-// f(integral_constant<int, 0>), f(<1>), ... in order
-template <class F, int... I>
-__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-
-constexpr int scrub_rows_slabs(int k, int e) { return (e == 1 && k <= 6) ? 8 : 4; }  // scrub_crc_slabs's rule
-
-}  // namespace
 
 // K survivors = the code's k, E extras (= rows of G, parity units all), SLABS
 // KiB of every cell per wave-tile, as gf_scrub_crc.
@@ -116,7 +73,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (uint32_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
         uint32_t lstripe, tcol;
         tile_coords(tile, a, lstripe, tcol);
-        // The scalar-length scheme of gf_reconstruct_crc_rows: the tile's
+        // The scalar-length scheme of gf_crc_rows (ec_rows_kernel.hpp): the tile's
         // coordinates and the stripe's logical bytes in SGPRs, lengths in 32
         // bits from r / 16 and r % 16 (the launcher keeps cell_len below
         // 2^31; a data unit starts at a multiple of 16).
@@ -388,7 +345,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 constexpr uint32_t kRowsByteTile = 4096;  // bytes of a stripe per block-tile
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void gf_scrub_rows_bytes(ScrubRowsBytesArgs a) {
-    using Spec = crc::Spec<KIND>;
     __shared__ uint32_t s_crc[256];
     __shared__ uint8_t s_exp[512];
     __shared__ uint8_t s_log[256];
@@ -396,18 +352,13 @@ __global__ __launch_bounds__(kBlock) void gf_scrub_rows_bytes(ScrubRowsBytesArgs
     __shared__ uint8_t s_syn[kScrubRowsMaxE][kBlock];  // this thread's syndromes at [j][tid]
     __shared__ unsigned long long s_res[2];
     const int tid = threadIdx.x;
-    s_crc[tid] = fused_tables<KIND>().slice[0][tid];
-    s_exp[tid] = kDevGf.exp[tid];
-    s_exp[tid + 256] = kDevGf.exp[tid + 256];
-    s_log[tid] = kDevGf.log[tid];
+    rows_stage_byte_tables<KIND>(s_crc, s_exp, s_log);
     for (int t = tid; t < kScrubRowsMaxE * kMaxK; t += kBlock) s_coef[t] = a.coef[t];
     __syncthreads();
     // clamped: the loops below stay inside the LDS arrays whatever the block holds
     const int k = min(max(a.ns, 0), kMaxK), m = min(max(a.e, 0), kScrubRowsMaxE);
     const uint64_t cell_len = a.cell_len, bpc = a.bytes_per_checksum;
     unsigned long long* const results = reinterpret_cast<unsigned long long*>(a.results);
-    auto stripe_r = [&](uint64_t s) { return a.lens.stripe_bytes ? a.lens.stripe_bytes[s] : a.lens.bytes; };
-    auto batch_stripe = [&](uint64_t s) -> uint64_t { return a.stripe_list ? a.stripe_list[s] : a.lens.stripe0 + s; };
 
     if (m > 0) {
         const uint64_t tps = (cell_len + kRowsByteTile - 1) / kRowsByteTile;
@@ -415,10 +366,10 @@ __global__ __launch_bounds__(kBlock) void gf_scrub_rows_bytes(ScrubRowsBytesArgs
         for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
             const uint64_t s = tile / tps;
             const uint64_t begin = (tile - s * tps) * kRowsByteTile;
-            const uint64_t r = stripe_r(s);
+            const uint64_t r = rows_stripe_bytes(a.lens, s);
             const uint64_t n0 = r < cell_len ? r : cell_len;
             if (begin >= n0) continue;  // block-uniform: nothing of the tile is read
-            const uint64_t stripe = batch_stripe(s);
+            const uint64_t stripe = rows_batch_stripe(a.stripe_list, a.lens, s);
             __syncthreads();  // the previous tile's findings are no longer read
             if (tid < 2) s_res[tid] = 0;
             __syncthreads();
@@ -477,18 +428,14 @@ __global__ __launch_bounds__(kBlock) void gf_scrub_rows_bytes(ScrubRowsBytesArgs
         const int i = int(rest / a.nck);
         const uint64_t chunk = rest - uint64_t(i) * a.nck;
         const uint64_t begin = chunk * bpc;
-        const uint64_t r = stripe_r(s);
+        const uint64_t r = rows_stripe_bytes(a.lens, s);
         const uint64_t n0 = r < cell_len ? r : cell_len;
         const uint64_t len = rows_unit_len(a.id[i], a.data_units, r, n0, cell_len);
         if (begin >= len) continue;
-        const uint64_t stripe = batch_stripe(s);
-        const uint64_t end = len - begin < bpc ? len : begin + bpc;
-        const uint8_t* p = a.in[i] + stripe * a.in_stride[i];
-        uint32_t crc = Spec::kInit;
-        for (uint64_t b = begin; b < end; b++) crc = crcdev::byte_step<Spec::kReflected, 1>(s_crc, crc, p[b]);
+        const uint64_t stripe = rows_batch_stripe(a.stripe_list, a.lens, s);
+        const uint32_t sum = rows_own_chunk_sum<KIND>(s_crc, a.in[i] + stripe * a.in_stride[i], begin, len, bpc);
         const uint64_t cell = stripe * a.n_total + a.id[i];
-        if (reinterpret_cast<const uint32_t*>(a.expected)[cell * a.nck + chunk] != __builtin_bswap32(crc ^ Spec::kXorout))
-            a.bad[cell] = 1;
+        if (reinterpret_cast<const uint32_t*>(a.expected)[cell * a.nck + chunk] != sum) a.bad[cell] = 1;
     }
 }
 
@@ -505,21 +452,14 @@ struct ScrubRowsFn {
 
 }  // namespace
 
-int launch_scrub_crc_rows(const MatmulArgs& in, const ScrubCrcArgs& cs, const ReconRowsLens& lens, int device,
+int launch_scrub_crc_rows(const MatmulArgs& a, const ScrubCrcArgs& cs, const ReconRowsLens& lens, int device,
                           hipStream_t stream) {
-    MatmulArgs a = in;
-    if (cs.kind != crc::kCrc32c && cs.kind != crc::kCksum) return -1;
-    if (a.k < 1 || a.k > kMaxK - kMaxR || a.r < 1 || a.r > kMaxR || a.cell_len == 0 || a.cell_len % 16 != 0 ||
-        !cs.expected || !cs.bad || !cs.results || cs.n_total == 0)
+    if (a.k < 1 || a.k > kMaxK - kMaxR || a.r < 1 || a.r > kMaxR || a.cell_len == 0 || !cs.expected || !cs.bad ||
+        !cs.results || cs.n_total == 0)
         return -1;
     if ((reinterpret_cast<uintptr_t>(cs.expected) & 3u) || (reinterpret_cast<uintptr_t>(cs.results) & 7u)) return -1;
-    if (reinterpret_cast<uintptr_t>(lens.stripe_bytes) & 7u) return -1;
-    if (!lens.stripe_bytes && (lens.bytes == 0 || lens.bytes > uint64_t(a.k) * a.cell_len)) return -1;
-    if (lens.stripe0 + a.stripes > 0xFFFFFFFFull || a.cell_len > 0x7FFFFFFFull) return -1;  // 32-bit lengths
     for (int i = 0; i < a.k + a.r; i++)
-        if (!a.in[i] || ((reinterpret_cast<uintptr_t>(a.in[i]) | a.in_stride[i]) & 15u) ||
-            cs.shard_id[i] >= cs.n_total)
-            return -1;
+        if (cs.shard_id[i] >= cs.n_total) return -1;
     for (int i = 0; i < a.k; i++)
         if (a.coef[i] == 0) return -1;  // the minors divide by row 0
     // S is the first k present units and data units have the lowest indices:
@@ -527,51 +467,28 @@ int launch_scrub_crc_rows(const MatmulArgs& in, const ScrubCrcArgs& cs, const Re
     // to extra 0)
     for (int j = 0; j < a.r; j++)
         if (cs.shard_id[a.k + j] < a.k) return -1;
-    const void* fn = pick_kr<ScrubRowsFn>(a.k, a.r, cs.kind);
-    if (!fn) return -1;
-    const Tune tn = tune_snapshot();
-    if (!tile_geometry(a, 4096u * scrub_rows_slabs(a.k, a.r))) return -1;
-    const uint64_t total = a.total_tiles;
-    if (total == 0) return 0;
-    // tile order and grid as launch_scrub_crc
-    set_tile_order(a, tn, 8u);
-    uint64_t grid = tn.grid ? uint64_t(tn.grid) : uint64_t(num_cus(device)) * (cs.stripe_list ? 2 : 4);
-    if (grid > total) grid = total;
-    ScrubCrcArgs c = cs;
-    ReconRowsLens l = lens;
-    void* args[] = {&a, &c, &l};
-    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(256), args, 0, stream);
-    return e == hipSuccess ? 0 : int(e);
+    // grid as launch_scrub_crc
+    return launch_rows_crc(pick_kr<ScrubRowsFn>(a.k, a.r, cs.kind), scrub_rows_slabs(a.k, a.r), a, cs, lens, a.k + a.r, 0,
+                           cs.stripe_list ? 2 : 4, device, stream);
 }
 
 int launch_scrub_rows_bytes(const ScrubRowsBytesArgs& in, int device, hipStream_t stream) {
     ScrubRowsBytesArgs a = in;
-    if (a.kind != crc::kCrc32c && a.kind != crc::kCksum) return -1;
-    if (a.ns < 0 || a.ns > kMaxK || a.e < 0 || a.e > kScrubRowsMaxE || a.ns + a.e < 1 || a.bytes_per_checksum == 0 ||
-        a.cell_len == 0 || !a.expected || !a.bad || (reinterpret_cast<uintptr_t>(a.expected) & 3u) ||
-        (reinterpret_cast<uintptr_t>(a.lens.stripe_bytes) & 7u))
+    if (a.ns < 0 || a.ns > kMaxK || a.e < 0 || a.e > kScrubRowsMaxE || a.ns + a.e < 1 || !a.expected || !a.bad ||
+        (reinterpret_cast<uintptr_t>(a.expected) & 3u) || !rows_bytes_args_ok(a, a.data_units))
         return -1;
     if (a.e > 0 && (!a.results || (reinterpret_cast<uintptr_t>(a.results) & 7u))) return -1;
-    if (!a.lens.stripe_bytes && (a.lens.bytes == 0 || a.lens.bytes > uint64_t(a.data_units) * a.cell_len)) return -1;
     for (int i = 0; i < a.ns + a.e; i++)
         if (!a.in[i] || a.id[i] >= a.n_total) return -1;
     for (int j = 0; j < a.e; j++)
         if (a.id[a.ns + j] < a.data_units) return -1;  // an extra is a parity unit
     if (a.stripes == 0) return 0;
-    a.nck = a.cell_len / a.bytes_per_checksum + (a.cell_len % a.bytes_per_checksum != 0);
+    a.nck = rows_nck(a.cell_len, a.bytes_per_checksum);
     const uint64_t tps = (a.cell_len + kRowsByteTile - 1) / kRowsByteTile;
     if (tps > 0xFFFFFFFFFFFFFFFFull / a.stripes) return -1;
-    const uint64_t tiles = a.e > 0 ? tps * a.stripes : 0;
-    const uint64_t items = a.nck * uint64_t(a.ns + a.e) * a.stripes;
-    uint64_t grid = (items + kBlock - 1) / kBlock;
-    if (grid < tiles) grid = tiles;
-    const uint64_t cap = uint64_t(num_cus(device)) * 8;
-    if (grid > cap) grid = cap;
-    const void* fn = a.kind == crc::kCrc32c ? reinterpret_cast<const void*>(&gf_scrub_rows_bytes<crc::kCrc32c>)
-                                            : reinterpret_cast<const void*>(&gf_scrub_rows_bytes<crc::kCksum>);
-    void* args[] = {&a};
-    const hipError_t e = hipLaunchKernel(fn, dim3(uint32_t(grid)), dim3(kBlock), args, 0, stream);
-    return e == hipSuccess ? 0 : int(e);
+    // a block per tile of the parity check where there is one
+    return launch_rows_bytes(&gf_scrub_rows_bytes<crc::kCrc32c>, &gf_scrub_rows_bytes<crc::kCksum>, a,
+                             a.nck * uint64_t(a.ns + a.e) * a.stripes, a.e > 0 ? tps * a.stripes : 0, device, stream);
 }
 
 }  // namespace hec

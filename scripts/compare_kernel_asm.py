@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare two device assembly listings kernel by kernel.
 
-    compare_kernel_asm.py OLD.s NEW.s [--registers]
+    compare_kernel_asm.py OLD.s NEW.s [--registers] [--map 'REGEX=REPLACEMENT' ...]
 
 The listings are what `hipcc $(HIPFLAGS) --save-temps -c x.hip` leaves as
 x-hip-amdgcn-amd-amdhsa-gfx950.s.  Comments and .file/.ident/.loc lines are
@@ -10,7 +10,9 @@ counts, private and group segment sizes) is identical and its instruction
 lines differ at most in the order of the two sources of a commutative op.
 Prints one line per kernel (names through c++filt where there is one);
 --registers adds the resource lines, parent and new, of each kernel that
-differs.  Exit status 1 when a kernel differs.
+differs.  Each --map rewrites the mangled names of the new listing
+(re.sub on every line, in the order given), so that a kernel that was renamed
+is paired with the name it had.  Exit status 1 when a kernel differs.
 """
 import re
 import subprocess
@@ -22,10 +24,12 @@ COMMUTATIVE = re.compile(r"^(v|s)_(xor|or|and|add_u32|add_nc_u32|add_co_u32|min_
                          r"xnor|add_i32)(_b32|_b64|_e32|_e64)*$")
 
 
-def clean(path):
+def clean(path, maps=()):
     out = []
     for line in open(path):
         line = line.split(";", 1)[0].rstrip()
+        for pat, repl in maps:
+            line = pat.sub(repl, line)
         s = line.strip()
         if not s or s.startswith((".file", ".ident", ".loc")) or "__hip_cuid_" in s:
             continue
@@ -105,9 +109,16 @@ def resources(tag, name, m):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv, args, maps = sys.argv[1:], [], []
+    while argv:
+        a = argv.pop(0)
+        if a == "--map":
+            pat, repl = argv.pop(0).split("=", 1)
+            maps.append((re.compile(pat), repl))
+        elif not a.startswith("--"):
+            args.append(a)
     regs = "--registers" in sys.argv
-    old, new = clean(args[0]), clean(args[1])
+    old, new = clean(args[0]), clean(args[1], maps)
     ko, kn = kernels(old), kernels(new)
     mo, mn = metadata(old), metadata(new)
     names = sorted(set(ko) | set(kn))

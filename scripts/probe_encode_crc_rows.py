@@ -1,5 +1,5 @@
 """Measurement probe (GPU box): encode with chunk sums of short stripes
-(hec_encode_crc_rows_device[_mixed]: gf_encode_crc_rows) against what a caller
+(hec_encode_crc_rows_device[_mixed]: gf_crc_rows<RowsEncode>) against what a caller
 pays without it, hec_encode_crc_device over the same stripes zero-padded and
 treated as full cells (a yardstick for time only: its sums of cut units are not
 the wanted ones).  One MI355X, product library, one process, the same buffers,
@@ -9,7 +9,7 @@ back-to-back repetitions, medians.
 Batch: RS(6,3) 1 MiB x 1024 and RS(10,4) 1 MiB x 256.
   (a)  every stripe full, uniform form (data_len == 0): the same launches as
        hec_encode_crc_device, so it must tie.
-  (a') the same full stripes forced through gf_encode_crc_rows: the mixed form
+  (a') the same full stripes forced through gf_crc_rows<RowsEncode>: the mixed form
        with one short stripe appended, against hec_encode_crc_device over all
        of them.  What a full stripe costs in the rows kernel.
   (b)  every stripe short, r seeded uniform in [1, k * cell_len), mixed form.

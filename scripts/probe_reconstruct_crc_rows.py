@@ -1,5 +1,5 @@
 """Measurement probe (GPU box): verified reconstruction of short stripes
-(hec_reconstruct_crc_rows_device[_mixed]: gf_reconstruct_crc_rows) against
+(hec_reconstruct_crc_rows_device[_mixed]: gf_crc_rows<RowsRepair>) against
 hec_reconstruct_crc_device[_mixed], on one MI355X, product library, one
 process, the same buffers, CRC32C per 512-B chunk, a warm call, rounds
 alternated, HIP events around REPS back-to-back repetitions.

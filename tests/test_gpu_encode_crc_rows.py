@@ -1,7 +1,7 @@
 """Encode with chunk sums of short stripes on the GPU:
 hec_encode_crc_rows_device (data_len: a short last stripe) and
 hec_encode_crc_rows_device_mixed (one length per stripe) -- the one-pass
-gf_encode_crc_rows kernel and the byte-wise gf_encode_rows_bytes.  Ground truth
+gf_crc_rows<RowsEncode> kernel and the byte-wise gf_encode_rows_bytes.  Ground truth
 is the CPU oracle throughout: random data cut at the length, the oracle's parity
 (O.codec_matrix(codec, k, m)[k:]) of the zero-padded cells, the oracle's chunk
 sums of each unit's true bytes.  The whole-buffer-image discipline of
@@ -178,7 +178,7 @@ def tile_of(k):
 @pytest.mark.parametrize("cell", [9232, 50192])
 @pytest.mark.parametrize("k,m", [(6, 3), (3, 2), (10, 4), (2, 1)])
 def test_short_last_stripe_fused_shapes(dev, k, m, cell, ctype):
-    """gf_encode_crc_rows behind the full stripes' launch: every length."""
+    """gf_crc_rows<RowsEncode> behind the full stripes' launch: every length."""
     S = 3
     cod = coder(k, m)
     full = k * cell
@@ -334,7 +334,7 @@ def test_full_stripes_identical_to_encode_crc(dev, cell):
 @pytest.mark.parametrize("k,m", [(6, 3), (10, 4)])
 def test_full_stripes_through_the_rows_kernel(dev, k, m):
     """One short stripe among 8 full ones, mixed form: all nine stripes run
-    gf_encode_crc_rows, and the full ones' parity and sums are the oracle's."""
+    gf_crc_rows<RowsEncode>, and the full ones' parity and sums are the oracle's."""
     cell = 9232
     full = k * cell
     rs = [full] * 9

@@ -1,7 +1,7 @@
 """Verified reconstruction of short stripes on the GPU:
 hec_reconstruct_crc_rows_device (data_len: a short last stripe) and
 hec_reconstruct_crc_rows_device_mixed (one length per stripe) -- the one-pass
-gf_reconstruct_crc_rows kernel and the byte-wise gf_reconstruct_rows_bytes.
+gf_crc_rows<RowsRepair> kernel and the byte-wise gf_reconstruct_rows_bytes.
 Ground truth is the CPU oracle throughout, as test_gpu_reconstruct_sums.py's
 short_group builds it: random data cut at the length, the oracle's parity of
 the zero-padded cells, the oracle's chunk sums of each unit's true bytes.  The
@@ -265,7 +265,7 @@ def last_short(k, cell, S, data_len):
 @pytest.mark.parametrize("cell", [9232, 50192])
 @pytest.mark.parametrize("k,m", [(6, 3), (3, 2), (10, 4), (2, 1)])
 def test_short_last_stripe_fused_shapes(dev, k, m, cell, ctype):
-    """gf_reconstruct_crc_rows behind the full stripes' gf_reconstruct_crc:
+    """gf_crc_rows<RowsRepair> behind the full stripes' gf_reconstruct_crc:
     every length, short_losses' five losses per length, d_expected absent /
     separate / the sums array, out of place and in place, by rotation."""
     S = 3
