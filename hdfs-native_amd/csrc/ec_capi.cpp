@@ -37,6 +37,7 @@
 #include "checksum_tables.hpp"
 #include "crc_compose.hpp"
 #include "ec_encode_rows.hpp"
+#include "ec_read_rows.hpp"
 #include "ec_kernels.hpp"
 #include "ec_reconstruct_crc.hpp"
 #include "ec_reconstruct_rows.hpp"
@@ -4180,6 +4181,313 @@ int hec_encode_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const ui
         return encode_rows_launch(c, kind, hec::ReconRowsLens{static_cast<const uint64_t*>(d_workspace), 0, 0}, d_data,
                                   data_strides, d_parity, parity_strides, cell_len, stripes, bytes_per_checksum,
                                   d_sums, stream);
+    });
+}
+
+// ---- verified striped read into a file-order buffer ----------------------------
+// hec_read_crc_rows_device*: the survivors verified over their own bytes, the
+// lost data units rebuilt, all k data units of every stripe written at their
+// file-order place, each for its own length (ec_read_rows.hip).  The mirror of
+// hec_encode_crc_rows_device*.
+
+}  // extern "C"
+
+namespace {
+
+// One present mask of a read and what its stripes run with: the survivors
+// (the first k present units, so every present data unit is one) and the lost
+// data units, both ascending.  `plan` holds the lost units' rows over the
+// survivors (its first e rows); null when no data unit is lost.
+struct ReadRowsGroup {
+    uint64_t mask = 0;
+    PlanRef plan;
+    std::vector<uint8_t> survivors;  // k
+    std::vector<uint8_t> lost;       // e
+    size_t first = 0, count = 0;     // its stripes: list[first] .. list[first + count - 1]
+};
+
+// The groups of a batch in the order their masks first appear, every stripe
+// once in `list` (by group, ascending within one) and its logical bytes beside
+// it, 0 rewritten to k * cell_len.
+struct ReadRowsPlan {
+    std::vector<ReadRowsGroup> groups;
+    std::vector<uint32_t> list;
+    std::vector<uint64_t> bytes;
+};
+
+// Survivors and lost data units of one mask.  HEC_ERR_NOT_ENOUGH_SHARDS with
+// fewer than k units present.  Host only.
+int read_rows_group(hec_coder* c, uint64_t mask, ReadRowsGroup* g) {
+    const size_t k = c->k;
+    g->mask = mask;
+    g->plan.reset();
+    g->survivors.clear();
+    g->lost.clear();
+    if ((mask & unit_bits(k)) == unit_bits(k)) {  // e = 0: the data units, no parity unit touched
+        for (size_t u = 0; u < k; u++) g->survivors.push_back(uint8_t(u));
+        return HEC_OK;
+    }
+    RowPlan rp;
+    const int rc = decode_rows(c, mask, &rp);
+    if (rc != HEC_OK) return rc;
+    g->plan = rp.plan;
+    for (size_t u : rp.plan->survivors) g->survivors.push_back(uint8_t(u));
+    for (size_t u : rp.plan->missing) g->lost.push_back(uint8_t(u));
+    return HEC_OK;
+}
+
+// Groups the stripes of a batch by present[s] (bits k + m and above ignored).
+// stripe_bytes = null: all full.  Nothing is queued; the first mask that has
+// no plan ends the call with its status.  Host only.
+int read_rows_plan(hec_coder* c, const uint64_t* present, const uint64_t* stripe_bytes, size_t stripes, size_t cell_len,
+                   ReadRowsPlan* p) {
+    const uint64_t all = unit_bits(c->k + c->m), full = uint64_t(c->k) * cell_len;
+    std::unordered_map<uint64_t, uint32_t> ids;
+    std::vector<uint32_t> group_of(stripes);
+    for (size_t s = 0; s < stripes; s++) {
+        const uint64_t mask = present[s] & all;
+        auto it = ids.find(mask);
+        if (it == ids.end()) {
+            ReadRowsGroup g;
+            const int rc = read_rows_group(c, mask, &g);
+            if (rc != HEC_OK) return rc;
+            it = ids.emplace(mask, uint32_t(p->groups.size())).first;
+            p->groups.push_back(std::move(g));
+        }
+        group_of[s] = it->second;
+        p->groups[it->second].count++;
+    }
+    size_t at = 0;
+    for (ReadRowsGroup& g : p->groups) {
+        g.first = at;
+        at += g.count;
+        g.count = 0;
+    }
+    p->list.resize(stripes);
+    p->bytes.resize(stripes);
+    for (size_t s = 0; s < stripes; s++) {
+        ReadRowsGroup& g = p->groups[group_of[s]];
+        const size_t i = g.first + g.count++;
+        p->list[i] = uint32_t(s);
+        p->bytes[i] = (!stripe_bytes || stripe_bytes[s] == 0) ? full : stripe_bytes[s];
+    }
+    return HEC_OK;
+}
+
+// The workspace: [stripe lists: u32 x stripes][pad to kAlign][their bytes: u64 x stripes].
+struct ReadRowsLayout {
+    size_t bytes_pos, need;
+};
+
+ReadRowsLayout read_rows_layout(size_t stripes) {
+    ReadRowsLayout w;
+    w.bytes_pos = align_up(stripes * sizeof(uint32_t));
+    w.need = w.bytes_pos + stripes * sizeof(uint64_t);
+    return w;
+}
+
+size_t read_rows_workspace(size_t stripes) { return read_rows_layout(stripes).need; }
+
+// Writes every byte of the image (lists, zeroes in the pad, lengths).
+void write_read_rows_image(uint8_t* host, const ReadRowsPlan& p, const ReadRowsLayout& w) {
+    const size_t list_bytes = p.list.size() * sizeof(uint32_t);
+    if (list_bytes) std::memcpy(host, p.list.data(), list_bytes);
+    std::memset(host + list_bytes, 0, w.bytes_pos - list_bytes);
+    if (!p.bytes.empty()) std::memcpy(host + w.bytes_pos, p.bytes.data(), p.bytes.size() * sizeof(uint64_t));
+}
+
+// What both entry points check before the coder's device is looked at, behind
+// recon_rows_check and the lengths.
+int read_rows_stride_check(const hec_coder* c, size_t cell_len, size_t file_stride) {
+    return file_stride != 0 && file_stride < c->k * cell_len ? HEC_ERR_INVALID_ARG : HEC_OK;
+}
+
+// ... and behind it.
+int read_rows_buffers_check(const uint8_t* const* d_shards, const size_t* shard_strides, const uint8_t* d_file,
+                            const uint8_t* d_expected, const uint8_t* d_bad) {
+    if (!d_shards || !shard_strides || !d_file || (d_expected && !d_bad) ||
+        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
+        return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// `stripes` stripes of one group (d_list, or lens.stripe0 on): gf_read_rows
+// where the launcher takes the shape, else gf_read_rows_bytes over the lost
+// data units, four per launch, the first launch verifying every survivor and
+// copying the present data units.
+int read_rows_launch(hec_coder* c, int kind, const ReadRowsGroup& g, const uint32_t* d_list, size_t stripes,
+                     const hec::ReconRowsLens& lens, const uint8_t* const* d_shards, const size_t* shard_strides,
+                     uint8_t* d_file, size_t file_stride, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                     uint8_t* d_bad, hipStream_t stream) {
+    if (stripes == 0) return HEC_OK;
+    const size_t k = c->k, n = c->k + c->m, e = g.lost.size();
+    if (bpc == 512 && e <= size_t(hec::kMaxR)) {
+        hec::MatmulArgs a;
+        std::memset(&a, 0, sizeof(a));
+        hec::ReadRowsCrcArgs cs;
+        std::memset(&cs, 0, sizeof(cs));
+        for (size_t i = 0; i < k; i++) {
+            const size_t u = g.survivors[i];
+            a.in[i] = d_shards[u];
+            a.in_stride[i] = shard_strides[u];
+            cs.shard_id[i] = uint8_t(u);
+        }
+        for (size_t j = 0; j < e; j++) {
+            cs.shard_id[k + j] = g.lost[j];
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = g.plan->matrix[j * k + i];
+        }
+        a.k = int32_t(k);
+        a.r = int32_t(e);
+        a.cell_len = cell_len;
+        a.stripes = stripes;
+        cs.expected = d_expected;
+        cs.bad = d_bad;
+        cs.file = d_file;
+        cs.file_stride = file_stride;
+        cs.n_total = uint32_t(n);
+        cs.kind = kind;
+        cs.stripe_list = d_list;
+        const int rc = hec::launch_read_crc_rows(a, cs, lens, c->device, stream);
+        if (rc == 0) return HEC_OK;
+        if (rc > 0) return to_status(rc);
+        // -1: refused, nothing launched
+    }
+    hec::ReadRowsBytesArgs a;
+    std::memset(&a, 0, sizeof(a));
+    size_t data_in = 0;
+    for (size_t i = 0; i < k; i++) {
+        const size_t u = g.survivors[i];
+        a.in[i] = d_shards[u];
+        a.in_stride[i] = shard_strides[u];
+        a.in_id[i] = uint8_t(u);
+        data_in += u < k;
+    }
+    a.k = int32_t(k);
+    a.n_total = uint32_t(n);
+    a.file = d_file;
+    a.file_stride = file_stride;
+    a.expected = d_expected;
+    a.bad = d_bad;
+    a.kind = kind;
+    a.stripe_list = d_list;
+    a.stripes = stripes;
+    a.lens = lens;
+    a.cell_len = cell_len;
+    a.bytes_per_checksum = bpc;
+    a.parity_in = d_expected ? int32_t(k - data_in) : 0;
+    for (size_t j0 = 0; j0 == 0 || j0 < e; j0 += size_t(hec::kMaxR)) {
+        const size_t rn = std::min(size_t(hec::kMaxR), e - j0);
+        std::memset(a.coef, 0, sizeof(a.coef));
+        std::memset(a.role, hec::kReadRowsSkip, sizeof(a.role));
+        for (size_t i = 0; j0 == 0 && i < data_in; i++) a.role[g.survivors[i]] = uint8_t(i);
+        for (size_t j = 0; j < rn; j++) {
+            a.role[g.lost[j0 + j]] = uint8_t(hec::kReadRowsLost | j);
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = g.plan->matrix[(j0 + j) * k + i];
+        }
+        a.r = int32_t(rn);
+        const int rc = hec::launch_read_rows_bytes(a, c->device, stream);
+        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+        a.expected = nullptr;  // the survivors are verified once
+        a.bad = nullptr;
+        a.parity_in = 0;
+    }
+    return HEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hec_read_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                             const size_t* shard_strides, uint8_t* d_file, size_t file_stride, size_t cell_len,
+                             size_t stripes, size_t bytes_per_checksum, uint64_t data_len, const uint8_t* d_expected,
+                             uint8_t* d_bad, void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    hec::crc::Geometry geo;
+    if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
+        return HEC_ERR_INVALID_ARG;
+    if (read_rows_stride_check(c, cell_len, file_stride) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_read_crc_rows_device");
+    chk = read_rows_buffers_check(d_shards, shard_strides, d_file, d_expected, d_bad);
+    if (chk != HEC_OK) return chk;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    return guarded([&]() -> int {
+        uint64_t mask = 0;
+        for (size_t i = 0; i < c->k + c->m; i++)
+            if (d_shards[i]) mask |= uint64_t(1) << i;
+        ReadRowsGroup g;
+        int rc = read_rows_group(c, mask, &g);
+        if (rc != HEC_OK) return rc;
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const uint64_t full = uint64_t(c->k) * cell_len;
+        const size_t stride = file_stride ? file_stride : size_t(full);
+        // one launch over the stripes - 1 full stripes and one over the last,
+        // or one over all of them when the last is full too
+        const size_t n_full = geo.last_len == full ? stripes : stripes - 1;
+        rc = read_rows_launch(c, kind, g, nullptr, n_full, hec::ReconRowsLens{nullptr, full, 0}, d_shards, shard_strides,
+                              d_file, stride, cell_len, bytes_per_checksum, d_expected, d_bad, stream);
+        if (rc != HEC_OK || n_full == stripes) return rc;
+        return read_rows_launch(c, kind, g, nullptr, 1, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, d_shards,
+                                shard_strides, d_file, stride, cell_len, bytes_per_checksum, d_expected, d_bad, stream);
+    });
+}
+
+size_t hec_read_crc_rows_mixed_workspace_size(const hec_coder_t* c, size_t stripes) {
+    if (!c || stripes > SIZE_MAX / 16) return 0;
+    return read_rows_workspace(stripes);
+}
+
+int hec_read_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
+                                   const size_t* shard_strides, uint8_t* d_file, size_t file_stride,
+                                   const uint64_t* present, const uint64_t* stripe_bytes, size_t cell_len,
+                                   size_t stripes, size_t bytes_per_checksum, const uint8_t* d_expected, uint8_t* d_bad,
+                                   void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    int kind;
+    int chk = recon_rows_check(c, checksum_type, cell_len, bytes_per_checksum, &kind);
+    if (chk != HEC_OK) return chk;
+    if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
+    for (size_t s = 0; stripe_bytes && s < stripes; s++)
+        if (stripe_bytes[s] > uint64_t(c->k) * cell_len) return HEC_ERR_INVALID_ARG;
+    if (read_rows_stride_check(c, cell_len, file_stride) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    if (c->device == HEC_DEVICE_HOST) return host_only("hec_read_crc_rows_device_mixed");
+    chk = read_rows_buffers_check(d_shards, shard_strides, d_file, d_expected, d_bad);
+    if (chk != HEC_OK) return chk;
+    const ReadRowsLayout w = read_rows_layout(stripes);
+    if (!present || !d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 7u) || workspace_bytes < w.need)
+        return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    return guarded([&]() -> int {
+        // 1. the distinct masks, their survivors and lost data units (host);
+        // fail before anything is queued
+        ReadRowsPlan plan;
+        int rc = read_rows_plan(c, present, stripe_bytes, stripes, cell_len, &plan);
+        if (rc != HEC_OK) return rc;
+        for (const ReadRowsGroup& g : plan.groups)
+            for (uint8_t u : g.survivors)
+                if (!d_shards[u]) return HEC_ERR_INVALID_ARG;  // a survivor needs storage
+        DeviceGuard dg(c->device);
+        if (!dg.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        // 2. the lists and lengths, one copy
+        uint8_t* ws = static_cast<uint8_t*>(d_workspace);
+        rc = upload_pinned(c, w.need, ws, stream, [&](uint8_t* host) { write_read_rows_image(host, plan, w); });
+        if (rc != HEC_OK) return rc;
+        // 3. one launch per mask over its stripes, full and short together
+        const uint32_t* d_list = reinterpret_cast<const uint32_t*>(ws);
+        const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
+        const size_t stride = file_stride ? file_stride : c->k * cell_len;
+        for (const ReadRowsGroup& g : plan.groups) {
+            rc = read_rows_launch(c, kind, g, d_list + g.first, g.count, hec::ReconRowsLens{d_bytes + g.first, 0, 0},
+                                  d_shards, shard_strides, d_file, stride, cell_len, bytes_per_checksum, d_expected,
+                                  d_bad, stream);
+            if (rc != HEC_OK) return rc;
+        }
+        return HEC_OK;
     });
 }
 

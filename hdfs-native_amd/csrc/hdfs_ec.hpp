@@ -383,6 +383,49 @@ class Coder {
                                                bytes_per_checksum, d_sums, d_workspace, workspace_bytes, hip_stream));
     }
 
+    // Verified striped read into a file-order buffer
+    // (hec_read_crc_rows_device): d_units[k+m] (nullptr = lost for the batch),
+    // the survivors verified against d_expected (nullptr = no verification)
+    // with flags in d_bad, the lost data units rebuilt, and data unit u of
+    // stripe s written to d_file + s * file_stride + u * cell_len (file_stride
+    // 0 = k * cell_len) for its own length; data_len as for
+    // encode_crc_rows_device, nothing at or past a stripe's logical end is
+    // written.  d_file must not overlap a unit's slot.
+    void read_crc_rows_device(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                              const std::vector<size_t>& strides, uint8_t* d_file, size_t file_stride, size_t cell_len,
+                              size_t stripes, size_t bytes_per_checksum, uint64_t data_len, const uint8_t* d_expected,
+                              uint8_t* d_bad, void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("read_crc_rows_device: need data_units + parity_units units");
+        check(hec_read_crc_rows_device(h_.get(), checksum_type, d_units.data(), strides.data(), d_file, file_stride,
+                                       cell_len, stripes, bytes_per_checksum, data_len, d_expected, d_bad, hip_stream));
+    }
+    // One presence mask and one length per stripe
+    // (hec_read_crc_rows_device_mixed): present[s] bit i = unit i of stripe s
+    // is present, stripe_bytes (nullptr = every stripe full) as for
+    // encode_crc_rows_device_mixed; d_workspace of
+    // read_crc_rows_mixed_workspace_size(stripes) bytes, 8-byte aligned, always
+    // needed, untouched until the stream has passed the call.
+    size_t read_crc_rows_mixed_workspace_size(size_t stripes) const {
+        return hec_read_crc_rows_mixed_workspace_size(h_.get(), stripes);
+    }
+    void read_crc_rows_device_mixed(int checksum_type, const std::vector<const uint8_t*>& d_units,
+                                    const std::vector<size_t>& strides, uint8_t* d_file, size_t file_stride,
+                                    const std::vector<uint64_t>& present, const std::vector<uint64_t>* stripe_bytes,
+                                    size_t cell_len, size_t bytes_per_checksum, const uint8_t* d_expected,
+                                    uint8_t* d_bad, void* d_workspace, size_t workspace_bytes,
+                                    void* hip_stream = nullptr) const {
+        if (d_units.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("read_crc_rows_device_mixed: need data_units + parity_units units");
+        if (stripe_bytes && stripe_bytes->size() != present.size())
+            throw std::invalid_argument("read_crc_rows_device_mixed: one length per stripe");
+        check(hec_read_crc_rows_device_mixed(h_.get(), checksum_type, d_units.data(), strides.data(), d_file,
+                                             file_stride, present.data(),
+                                             stripe_bytes ? stripe_bytes->data() : nullptr, cell_len, present.size(),
+                                             bytes_per_checksum, d_expected, d_bad, d_workspace, workspace_bytes,
+                                             hip_stream));
+    }
+
     // Verified reconstruction of a device-resident batch, asynchronous on
     // hip_stream (hec_reconstruct_crc_device): d_units[k+m] (nullptr =
     // missing) are rebuilt into d_out[t] (may be the lost unit's own slot) and

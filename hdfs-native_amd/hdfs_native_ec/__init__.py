@@ -73,6 +73,7 @@ EXPORTS = [
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
     "hec_scrub_crc_rows_device", "hec_scrub_crc_rows_mixed_workspace_size", "hec_scrub_crc_rows_device_mixed",
     "hec_encode_crc_rows_device", "hec_encode_crc_rows_mixed_workspace_size", "hec_encode_crc_rows_device_mixed",
+    "hec_read_crc_rows_device", "hec_read_crc_rows_mixed_workspace_size", "hec_read_crc_rows_device_mixed",
     "hec_crc_concat", "hec_composite_crc", "hec_composite_crc_workspace_size", "hec_composite_crc_device",
 ]
 
@@ -222,6 +223,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_encode_crc_rows_mixed_workspace_size": ([P, S], S),
         "hec_encode_crc_rows_device_mixed": ([P, I, PP, SP, PP, SP, ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, S,
                                               P], I),
+        "hec_read_crc_rows_device": ([P, I, PP, SP, P, S, S, S, S, ctypes.c_uint64, P, P, P], I),
+        "hec_read_crc_rows_mixed_workspace_size": ([P, S], S),
+        "hec_read_crc_rows_device_mixed": ([P, I, PP, SP, P, S, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint64), S, S, S, P, P, P, S, P], I),
         "hec_crc_concat": ([I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)], I),
         "hec_composite_crc": ([I, P, S, S, S, S, S, ctypes.c_uint64, P, P, P], I),
         "hec_composite_crc_workspace_size": ([S, S], S),
@@ -825,6 +830,41 @@ class Coder:
             _sp(parity_strides), lens, cell_len, stripes, bytes_per_checksum, ctypes.c_void_p(sums_ptr),
             ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)))
 
+    def read_crc_rows_device(self, shard_ptrs, shard_strides, file_ptr, cell_len, stripes, file_stride: int = 0,
+                             data_len: int = 0, expected_ptr=None, bad_ptr=None, bytes_per_checksum: int = 512,
+                             checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_read_crc_rows_device: the verified striped read into a
+        file-order buffer.  shard_ptrs[k+m] (None / 0 = lost for the batch);
+        data unit u of stripe s goes to file_ptr + s * file_stride + u *
+        cell_len (file_stride 0 = k * cell_len) for its own length, copied or
+        rebuilt; data_len as for encode_crc_rows_device.  With expected_ptr the
+        survivors are verified and bad_ptr's flags set."""
+        _check(self._lib.hec_read_crc_rows_device(
+            self._h, checksum_type, None if shard_ptrs is None else _pp([p or 0 for p in shard_ptrs]),
+            None if shard_strides is None else _sp(shard_strides), ctypes.c_void_p(file_ptr), file_stride, cell_len,
+            stripes, bytes_per_checksum, data_len, ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+            ctypes.c_void_p(stream)))
+
+    def read_crc_rows_mixed_workspace_size(self, stripes: int) -> int:
+        return self._lib.hec_read_crc_rows_mixed_workspace_size(self._h, stripes)
+
+    def read_crc_rows_device_mixed(self, shard_ptrs, shard_strides, file_ptr, present_masks, stripe_bytes, cell_len,
+                                   stripes, workspace_ptr, workspace_bytes, file_stride: int = 0, expected_ptr=None,
+                                   bad_ptr=None, bytes_per_checksum: int = 512,
+                                   checksum_type: int = CHECKSUM_CRC32C, stream: int = 0) -> None:
+        """hec_read_crc_rows_device_mixed: read_crc_rows_device with one
+        presence mask per stripe and the logical bytes of every stripe
+        (stripe_bytes[s]; None = all full; 0 or k * cell_len = that stripe is
+        full).  The workspace (read_crc_rows_mixed_workspace_size(stripes)
+        bytes, 8-byte aligned) is always needed."""
+        masks = None if present_masks is None else (ctypes.c_uint64 * max(stripes, 1))(*present_masks)
+        lens = None if stripe_bytes is None else (ctypes.c_uint64 * max(stripes, 1))(*stripe_bytes)
+        _check(self._lib.hec_read_crc_rows_device_mixed(
+            self._h, checksum_type, None if shard_ptrs is None else _pp([p or 0 for p in shard_ptrs]),
+            None if shard_strides is None else _sp(shard_strides), ctypes.c_void_p(file_ptr), file_stride, masks, lens,
+            cell_len, stripes, bytes_per_checksum, ctypes.c_void_p(expected_ptr), ctypes.c_void_p(bad_ptr),
+            ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream)))
+
     def decode_mixed_workspace_size(self, stripes: int) -> int:
         return self._lib.hec_decode_mixed_workspace_size(self._h, stripes)
 
@@ -1265,6 +1305,52 @@ def encode_crc_rows_batch(coder: Coder, cells, sums, data_len: int = 0, stripe_b
                                        cells.shape[2], S, sums.data_ptr(), workspace.data_ptr(), workspace.numel(),
                                        bytes_per_checksum=bytes_per_checksum, checksum_type=checksum_type,
                                        stream=s.cuda_stream)
+    return workspace
+
+
+def read_crc_rows_batch(coder: Coder, cells, present_masks: Sequence[int], expected, file, data_len: int = 0,
+                        stripe_bytes=None, bad=None, file_stride: int = 0, checksum_type: int = CHECKSUM_CRC32C,
+                        bytes_per_checksum: int = 512, stream=None, workspace=None):
+    """The verified striped read of a batch into file order: cells is a uint8
+    cuda tensor [S, k+m, width], present_masks[s] the units stripe s has,
+    expected the [S, k+m, nck] sums array (None = no verification), file a
+    uint8 cuda tensor that receives data unit u of stripe s at s * file_stride
+    + u * width (file_stride 0 = k * width) for its own length, and bad the
+    zeroed [S, k+m] flags.  With one mask for all stripes and no stripe_bytes
+    the uniform form runs with data_len (0 = every stripe full), else the mixed
+    form with stripe_bytes (0 or k * width = that stripe is full).  Nothing at
+    or past a stripe's logical end is written.  Returns the workspace the mixed
+    form allocated or was given (reusable once the stream has passed the
+    call), or None."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    kw = dict(file_stride=file_stride, expected_ptr=None if expected is None else expected.data_ptr(),
+              bad_ptr=None if bad is None else bad.data_ptr(), bytes_per_checksum=bytes_per_checksum,
+              checksum_type=checksum_type, stream=s.cuda_stream)
+    masks = list(present_masks)
+    if stripe_bytes is None and len(set(masks)) <= 1:
+        mask = masks[0] if masks else (1 << n) - 1
+        coder.read_crc_rows_device([p if (mask >> i) & 1 else None for i, p in enumerate(ptrs)], strides,
+                                   file.data_ptr(), cells.shape[2], S, data_len=data_len, **kw)
+        return None
+    if data_len and stripe_bytes is not None:
+        raise ValueError("read_crc_rows_batch: data_len or stripe_bytes, not both")
+    if data_len:  # several masks: the last stripe's length goes into the mixed form
+        full = coder.data_units * cells.shape[2]
+        last = data_len - (S - 1) * full
+        if not 0 < last <= full:
+            raise ValueError("read_crc_rows_batch: data_len does not end in the last stripe")
+        stripe_bytes = [0] * (S - 1) + [last]
+    if workspace is None:
+        workspace = torch.empty(max(coder.read_crc_rows_mixed_workspace_size(S), 8), dtype=torch.uint8,
+                                device=cells.device)
+        workspace.record_stream(s)
+    coder.read_crc_rows_device_mixed(ptrs, strides, file.data_ptr(), masks,
+                                     None if stripe_bytes is None else list(stripe_bytes), cells.shape[2], S,
+                                     workspace.data_ptr(), workspace.numel(), **kw)
     return workspace
 
 

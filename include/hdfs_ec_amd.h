@@ -873,6 +873,81 @@ int hec_encode_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
                                      size_t bytes_per_checksum,
                                      uint8_t *d_sums, void *d_workspace, size_t workspace_bytes, void *hip_stream);
 
+/* ---- Verified striped read into a file-order buffer ------------------------ *
+ * The reader's side of hec_encode_crc_rows_device* (StripedBlockStream::
+ * read_slice on the device): one pass that verifies the survivors' chunk sums,
+ * rebuilds the lost data units and writes all k data units of every stripe at
+ * their file-order place, each cut to its own length.  Write -> read works on
+ * one file-order buffer and one sums array, with no padding on either side.
+ * Geometry (r, n0, len(u)), data_len (uniform form), stripe_bytes (mixed form,
+ * host array, NULL = every stripe full, 0 or k*cell_len = full, above that
+ * HEC_ERR_INVALID_ARG), present (host array, bit i of present[s] = unit i of
+ * stripe s is present), the [stripe][k+m][nck] layout of d_expected and the
+ * [stripe][k+m] layout of d_bad are those of
+ * hec_reconstruct_crc_rows_device[_mixed].  d_shards[k+m] / shard_strides as
+ * there; in the uniform form a NULL entry is a unit lost for the whole batch, in
+ * the mixed form every unit that is a survivor of some stripe needs storage.
+ * The survivors of a stripe are its first k present units, so every present
+ * data unit is a survivor; e = its lost data units.  With e == 0, the common
+ * read, k units are read, verified and written and no parity unit is touched.
+ * Reads: no slot byte at or past len(u) influences anything; a unit that is
+ * empty in a stripe is not read; nothing at or past cell_len of a slot is read;
+ * on the 16-B aligned route a read may reach the end of the 16-byte block that
+ * holds byte n0-1, and no further.
+ * Output: data unit u < k of stripe s goes to d_file + s*file_stride +
+ * u*cell_len (file_stride == 0: k*cell_len) for exactly len(u) bytes, copied
+ * where it is present and rebuilt where it is lost.  There is no zero fill: no
+ * byte of row s at or past r(s) is written, and none between k*cell_len and
+ * file_stride.  In the uniform form with the default stride a buffer of exactly
+ * data_len bytes is enough (stripes*k*cell_len with data_len == 0).  Parity is
+ * never written, no sums are written, d_expected and the shards are read-only.
+ * d_file must not overlap any shard slot; this is not checked.
+ * Verification: with d_expected every survivor is verified over its own len(u)
+ * bytes and d_bad[s*(k+m) + u] = 1 is set on a mismatch (flags are only ever
+ * set: zero them first).  A stripe with a flagged survivor has unspecified
+ * bytes in its row's [0, r); everything else holds.  The caller clears the
+ * flagged unit from that stripe's mask and calls the mixed form again; there is
+ * no host re-plan inside.  d_expected == NULL (d_bad is then ignored) is the
+ * plain read.  checksum_type is HEC_CHECKSUM_CRC32C or HEC_CHECKSUM_CRC32 in
+ * either case; HEC_CHECKSUM_NULL and unknown types are HEC_ERR_INVALID_ARG.
+ * Checks, in this order, nothing queued on any error: coder, type, cell_len,
+ * bytes_per_checksum, data_len / stripe_bytes, a file_stride that is non-zero
+ * and below k*cell_len (HEC_ERR_INVALID_ARG); a host-only coder
+ * (HEC_ERR_DEVICE); NULL arrays, d_file NULL, d_expected without d_bad or not
+ * 4-byte aligned, the workspace (HEC_ERR_INVALID_ARG); stripes == 0 is HEC_OK.
+ * A pattern with fewer than k present units is HEC_ERR_NOT_ENOUGH_SHARDS.
+ * The calls are asynchronous and neither allocate nor read back.
+ * Uniform form: one launch over the stripes-1 full stripes and one over the
+ * last stripe with its r by value; a single launch when data_len == 0 or the
+ * last stripe is full.  Kernels only, capturable into a graph.
+ * Mixed form: one launch per distinct present mask over that mask's stripes,
+ * full and short together.  d_workspace
+ * (hec_read_crc_rows_mixed_workspace_size; 0 for a NULL coder) is always
+ * required: NULL, not 8-byte aligned or too small is HEC_ERR_INVALID_ARG.  It
+ * receives the masks' stripe lists and the u64 lengths (0 rewritten to
+ * k*cell_len) in one asynchronous copy and must stay untouched until the
+ * stream has passed the call; calls in flight at once need different
+ * workspaces.
+ * The one-pass kernel (k reads + k writes of live bytes) takes k in
+ * {2,3,6,10}, e <= 4, bytes_per_checksum == 512, 16-B aligned bases, strides,
+ * d_file, file_stride and cell_len (below 2^31); every other shape takes a
+ * byte-wise kernel with the same results.  All codecs (rs, xor, rs-legacy). */
+int hec_read_crc_rows_device(hec_coder_t *coder, int checksum_type,
+                             const uint8_t *const *d_shards, const size_t *shard_strides,
+                             uint8_t *d_file, size_t file_stride,
+                             size_t cell_len, size_t stripes, size_t bytes_per_checksum, uint64_t data_len,
+                             const uint8_t *d_expected, uint8_t *d_bad, void *hip_stream);
+
+size_t hec_read_crc_rows_mixed_workspace_size(const hec_coder_t *coder, size_t stripes);
+
+int hec_read_crc_rows_device_mixed(hec_coder_t *coder, int checksum_type,
+                                   const uint8_t *const *d_shards, const size_t *shard_strides,
+                                   uint8_t *d_file, size_t file_stride,
+                                   const uint64_t *present, const uint64_t *stripe_bytes,
+                                   size_t cell_len, size_t stripes, size_t bytes_per_checksum,
+                                   const uint8_t *d_expected, uint8_t *d_bad,
+                                   void *d_workspace, size_t workspace_bytes, void *hip_stream);
+
 /* The raw hot loop, Mul<&[&[u8]]> (matrix.rs:204-231), batched:
  * out[j] = sum_i matrix[j*cols + i] * in[i] for j < rows, i < cols.
  * Any rows >= 1 (launched 4 output rows at a time), 1 <= cols <=

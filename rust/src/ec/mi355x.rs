@@ -176,6 +176,17 @@ unsafe extern "C" {
                                         stripes: usize, bytes_per_checksum: usize, d_sums: *mut u8,
                                         d_workspace: *mut c_void, workspace_bytes: usize,
                                         stream: *mut c_void) -> c_int;
+    fn hec_read_crc_rows_device(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                shard_strides: *const usize, d_file: *mut u8, file_stride: usize, cell_len: usize,
+                                stripes: usize, bytes_per_checksum: usize, data_len: u64, d_expected: *const u8,
+                                d_bad: *mut u8, stream: *mut c_void) -> c_int;
+    fn hec_read_crc_rows_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
+    fn hec_read_crc_rows_device_mixed(c: *mut HecCoder, checksum_type: c_int, d_shards: *const *const u8,
+                                      shard_strides: *const usize, d_file: *mut u8, file_stride: usize,
+                                      present: *const u64, stripe_bytes: *const u64, cell_len: usize, stripes: usize,
+                                      bytes_per_checksum: usize, d_expected: *const u8, d_bad: *mut u8,
+                                      d_workspace: *mut c_void, workspace_bytes: usize,
+                                      stream: *mut c_void) -> c_int;
     fn hec_crc_concat(checksum_type: c_int, crc_a: u32, crc_b: u32, len_b: u64, out: *mut u32) -> c_int;
     fn hec_composite_crc(checksum_type: c_int, sums: *const u8, n_units: usize, data_units: usize, cell_len: usize,
                          stripes: usize, bytes_per_checksum: usize, data_len: u64, cell_crcs: *mut u8,
@@ -791,6 +802,67 @@ impl GpuCoder {
                                              parity.as_ptr(), parity_strides.as_ptr(),
                                              stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()), cell, stripes,
                                              bytes_per_checksum, sums, workspace, workspace_bytes, stream)
+        })
+    }
+
+    /// Verified striped read into a file-order buffer
+    /// (`hec_read_crc_rows_device`): `StripedBlockStream::read_slice` on the
+    /// device.  `shards[k + m]` (null = lost for the batch); the survivors are
+    /// verified against `expected` (null = no verification) with flags set in
+    /// `bad`, the lost data units rebuilt, and data unit u of stripe s written
+    /// to `file + s * file_stride + u * cell` (`file_stride` 0 = `k * cell`)
+    /// for its own length.  `data_len` as for `encode_crc_rows_device`; nothing
+    /// at or past a stripe's logical end is written.
+    ///
+    /// # Safety
+    /// `shards[i] + s * shard_strides[i]` must be device memory of `cell`
+    /// bytes for every present unit and stripe, `file` device memory that
+    /// covers every row's logical bytes and overlaps no shard slot,
+    /// `expected` / `bad` device memory of `stripes * (k + m) * nck * 4` /
+    /// `stripes * (k + m)` bytes, all valid until `stream` has passed the call.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn read_crc_rows_device(&self, checksum_type: i32, shards: &[*const u8], shard_strides: &[usize],
+                                       file: *mut u8, file_stride: usize, cell: usize, stripes: usize,
+                                       bytes_per_checksum: usize, data_len: u64, expected: *const u8, bad: *mut u8,
+                                       stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_read_crc_rows_device(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(), file,
+                                     file_stride, cell, stripes, bytes_per_checksum, data_len, expected, bad, stream)
+        })
+    }
+
+    /// Device bytes `read_crc_rows_device_mixed` needs for `stripes` stripes.
+    pub fn read_crc_rows_mixed_workspace_size(&self, stripes: usize) -> usize {
+        unsafe { hec_read_crc_rows_mixed_workspace_size(self.raw, stripes) }
+    }
+
+    /// `read_crc_rows_device` with one presence mask and the logical bytes of
+    /// every stripe (`hec_read_crc_rows_device_mixed`): bit i of `present[s]`
+    /// = unit i of stripe s is present; `stripe_bytes` (`None` = every stripe
+    /// full) has one entry per stripe, 0 or `k * cell` = that stripe is full.
+    /// `workspace` is device memory of
+    /// `read_crc_rows_mixed_workspace_size(stripes)` bytes (8-byte aligned),
+    /// always needed and untouched until `stream` has passed the call.
+    ///
+    /// # Safety
+    /// As `read_crc_rows_device`.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn read_crc_rows_device_mixed(&self, checksum_type: i32, shards: &[*const u8],
+                                             shard_strides: &[usize], file: *mut u8, file_stride: usize,
+                                             present: &[u64], stripe_bytes: Option<&[u64]>, cell: usize,
+                                             bytes_per_checksum: usize, expected: *const u8, bad: *mut u8,
+                                             workspace: *mut c_void, workspace_bytes: usize,
+                                             stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        assert!(stripe_bytes.map_or(true, |b| b.len() == present.len()), "one length per stripe");
+        check(unsafe {
+            hec_read_crc_rows_device_mixed(self.raw, checksum_type as c_int, shards.as_ptr(), shard_strides.as_ptr(),
+                                           file, file_stride, present.as_ptr(),
+                                           stripe_bytes.map_or(std::ptr::null(), |b| b.as_ptr()), cell, present.len(),
+                                           bytes_per_checksum, expected, bad, workspace, workspace_bytes, stream)
         })
     }
 
