@@ -2656,24 +2656,145 @@ int hec_decode_verify_device(hec_coder_t* c, int checksum_type, const uint8_t* c
 // (ec_reconstruct_crc.hip), or as a composition of internal launches where
 // the fused kernel does not take the shape.
 
+}  // extern "C"
+
 namespace {
 
-// One uniform group of stripes of a verified reconstruction: the rows of a
-// plan, and (mixed form) the device list of the group's stripes.
-struct CrcGroupCall {
-    const RowPlan* rp;
-    size_t stripes;            // stripes of the group (entries of d_list)
-    const uint32_t* d_list;    // null: stripes 0 .. stripes-1
+// Where the storage of units comes from: d_shards or d_out with their strides.
+template <typename P>
+struct UnitTable {
+    P const* base;
+    const size_t* stride;
 };
 
-// What every entry point checks the same way; kind < 0 = HEC_CHECKSUM_NULL.
-int recon_crc_check(const hec_coder* c, int checksum_type, size_t cell_len, size_t bpc, const uint8_t* d_expected,
-                    const uint8_t* d_bad, const uint8_t* d_sums, int* kind) {
+// What a verified call carries from its entry point to its launches; every
+// entry point builds one behind its argument checks.  The encode calls: the
+// shards are the data units, the outputs the parity units.
+struct VerifiedCall {
+    hec_coder* c;
+    int kind;  // crc::Kind
+    const uint8_t* const* d_shards;
+    const size_t* shard_strides;
+    uint8_t* const* d_out;  // null: the call writes no unit (sums only, scrub, read)
+    const size_t* out_strides;
+    size_t cell_len, bpc;
+    const uint8_t* d_expected;  // null: nothing verified
+    uint8_t* d_bad;
+    uint8_t* d_sums;  // null: the call writes no sums (scrub, read)
+    hipStream_t stream;
+    size_t k() const { return c->k; }
+    size_t n() const { return c->k + c->m; }
+    UnitTable<const uint8_t*> shards() const { return {d_shards, shard_strides}; }
+    UnitTable<uint8_t*> outs() const { return {d_out, out_strides}; }
+};
+
+// One group of stripes of a verified call that share a plan: its rows (null:
+// a scrub group without an extra, sums only) and (mixed form) the device list
+// of the group's stripes.
+struct CrcGroupCall {
+    const RowPlan* rp;
+    size_t stripes;          // stripes of the group (entries of d_list)
+    const uint32_t* d_list;  // null: stripes 0 .. stripes-1
+    uint64_t mask = 0;       // the scrub calls: the units the group's stripes have; unused elsewhere
+};
+
+// The slots of an argument block to fill, from the first one on: the units'
+// bases and strides (null: the block has none, as where only sums are
+// computed) and their indices.
+template <typename P, typename S>
+struct UnitSlots {
+    P* base;
+    S* stride;
+    uint8_t* id;
+};
+
+template <typename P, typename S>
+UnitSlots<P, S> unit_slots(P* base, S* stride, uint8_t* id) {
+    return {base, stride, id};
+}
+
+inline UnitSlots<uint8_t*, uint64_t> id_slots(uint8_t* id) { return {nullptr, nullptr, id}; }
+
+// The units of a checksum launch (checksum_launch's bases, strides, sid).
+struct UnitList {
+    const uint8_t* base[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t stride[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    uint8_t id[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    size_t cnt = 0;
+    UnitSlots<const uint8_t*, size_t> slots() { return {base, stride, id}; }
+};
+
+template <typename T, typename P, typename S>
+inline void fill_unit(size_t u, size_t slot, const UnitTable<T>& from, const UnitSlots<P, S>& to) {
+    if (to.base) {
+        to.base[slot] = from.base[u];
+        to.stride[slot] = from.stride[u];
+    }
+    to.id[slot] = uint8_t(u);
+}
+
+// `count` units of a list, in its order, into the slots.
+template <typename U, typename T, typename P, typename S>
+void fill_units(const U* units, size_t count, const UnitTable<T>& from, const UnitSlots<P, S>& to) {
+    for (size_t r = 0; r < count; r++) fill_unit(units[r], r, from, to);
+}
+
+// The k survivors of a plan into the slots.
+template <typename T, typename P, typename S>
+void fill_survivors(const RowPlan& rp, size_t k, const UnitTable<T>& from, const UnitSlots<P, S>& to) {
+    fill_units(rp.plan->rec_survivors.data(), k, from, to);
+}
+
+// Rows j0 .. j0+rn-1 of a plan: row j0 + j's unit into slot j, its
+// coefficients into coef[j*kMaxK + i].
+template <typename T, typename P, typename S>
+void fill_rows(const RowPlan& rp, size_t k, size_t j0, size_t rn, uint8_t* coef, const UnitTable<T>& from,
+               const UnitSlots<P, S>& to) {
+    const DecodePlan& p = *rp.plan;
+    for (size_t j = 0; j < rn; j++) {
+        const size_t row = rp.rows[j0 + j];
+        fill_unit(p.lost[row], j, from, to);
+        for (size_t i = 0; i < k; i++) coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
+    }
+}
+
+// The units of a mask, ascending; returns how many.
+size_t mask_units(uint64_t mask, uint8_t* units) {
+    size_t cnt = 0;
+    for (; mask; mask &= mask - 1) units[cnt++] = uint8_t(__builtin_ctzll(mask));
+    return cnt;
+}
+
+// A fused launcher's return as the helpers pass it on: 0 ok, -1 refused
+// (nothing launched), else HEC_*.
+int fused_status(int rc) { return rc <= 0 ? rc : to_status(rc); }
+
+// The byte route over `rows` rows, kMaxR per launch (one launch without a row
+// where `even_empty`): fill(j0, rn) sets the rows' slots and, from the second
+// launch on, clears what only the first launch does; launch() queues it.
+template <typename Fill, typename Launch>
+int byte_route_rows(size_t rows, bool even_empty, Fill&& fill, Launch&& launch) {
+    for (size_t j0 = 0; j0 < rows || (even_empty && j0 == 0); j0 += size_t(hec::kMaxR)) {
+        fill(j0, std::min(size_t(hec::kMaxR), rows - j0));
+        const int rc = launch();
+        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
+    }
+    return HEC_OK;
+}
+
+// What every entry point checks the same way, its buffers apart
+// (recon_sums_buffers_check); kind < 0 = HEC_CHECKSUM_NULL, which only a call
+// that can do without sums takes (`null_ok`).
+int recon_crc_check(const hec_coder* c, int checksum_type, bool null_ok, size_t cell_len, size_t bpc, int* kind) {
     if (!c || cell_len == 0) return HEC_ERR_INVALID_ARG;
     *kind = -1;
-    if (checksum_type == HEC_CHECKSUM_NULL) return HEC_OK;
+    if (null_ok && checksum_type == HEC_CHECKSUM_NULL) return HEC_OK;
     *kind = crc_kind(checksum_type);
-    if (*kind < 0 || bpc == 0 || !d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
+    return *kind < 0 || bpc == 0 ? HEC_ERR_INVALID_ARG : HEC_OK;
+}
+
+int recon_sums_buffers_check(const uint8_t* d_expected, const uint8_t* d_bad, const uint8_t* d_sums) {
+    if (!d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
         (reinterpret_cast<uintptr_t>(d_expected) & 3u))
         return HEC_ERR_INVALID_ARG;
     return HEC_OK;
@@ -2686,84 +2807,72 @@ bool recon_crc_shape(const hec_coder* c, size_t cell_len, size_t bpc) {
     return register_kernel_k(c->k) && bpc == 512 && cell_len % 16 == 0;
 }
 
-bool recon_crc_group_aligned(const hec_coder* c, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                             const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides) {
+// At most kMaxR rows, and 16-byte aligned survivors and (where the call
+// writes them) targets.
+bool recon_crc_group_aligned(const VerifiedCall& x, const CrcGroupCall& g) {
     if (g.rp->rows.size() > size_t(hec::kMaxR)) return false;
     uint64_t survivors = 0;
-    for (size_t r = 0; r < c->k; r++) survivors |= uint64_t(1) << g.rp->plan->rec_survivors[r];
-    return aligned16(d_shards, shard_strides, survivors) && aligned16(d_out, out_strides, g.rp->units());
+    for (size_t r = 0; r < x.k(); r++) survivors |= uint64_t(1) << g.rp->plan->rec_survivors[r];
+    return aligned16(x.d_shards, x.shard_strides, survivors) &&
+           (!x.d_out || aligned16(x.d_out, x.out_strides, g.rp->units()));
+}
+
+// The two argument blocks of a fused reconstruction launch over one group:
+// the survivors in, the group's rows out (x.d_out == null: their sums only).
+void recon_fused_args(const VerifiedCall& x, const CrcGroupCall& g, hec::MatmulArgs* a, hec::ReconCrcArgs* cs) {
+    const size_t k = x.k(), r = g.rp->rows.size();
+    std::memset(a, 0, sizeof(*a));
+    std::memset(cs, 0, sizeof(*cs));
+    fill_survivors(*g.rp, k, x.shards(), unit_slots(a->in, a->in_stride, cs->shard_id));
+    fill_rows(*g.rp, k, 0, r, a->coef, x.outs(),
+              x.d_out ? unit_slots(a->out, a->out_stride, cs->shard_id + k) : id_slots(cs->shard_id + k));
+    a->k = int32_t(k);
+    a->r = int32_t(r);
+    a->cell_len = x.cell_len;
+    a->stripes = g.stripes;
+    cs->sums = x.d_sums;
+    cs->expected = x.d_expected;
+    cs->bad = x.d_bad;
+    cs->n_total = uint32_t(x.n());
+    cs->kind = x.kind;
+    cs->stripe_list = g.d_list;
 }
 
 // The fused launch of one group.  0 ok, -1 refused by the launcher, else HEC_*.
-int recon_crc_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                    const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides, size_t cell_len,
-                    const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
-    const size_t k = c->k, n = c->k + c->m;
-    const DecodePlan& p = *g.rp->plan;
+int recon_crc_fused(const VerifiedCall& x, const CrcGroupCall& g) {
     hec::MatmulArgs a;
-    std::memset(&a, 0, sizeof(a));
     hec::ReconCrcArgs cs;
-    std::memset(&cs, 0, sizeof(cs));
-    for (size_t r = 0; r < k; r++) {
-        const size_t u = p.rec_survivors[r];
-        a.in[r] = d_shards[u];
-        a.in_stride[r] = shard_strides[u];
-        cs.shard_id[r] = uint8_t(u);
-    }
-    for (size_t j = 0; j < g.rp->rows.size(); j++) {
-        const size_t row = g.rp->rows[j], u = p.lost[row];
-        a.out[j] = d_out[u];
-        a.out_stride[j] = out_strides[u];
-        cs.shard_id[k + j] = uint8_t(u);
-        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-    }
-    a.k = int32_t(k);
-    a.r = int32_t(g.rp->rows.size());
-    a.cell_len = cell_len;
-    a.stripes = g.stripes;
-    cs.sums = d_sums;
-    cs.expected = d_expected;
-    cs.bad = d_bad;
-    cs.n_total = uint32_t(n);
-    cs.kind = kind;
-    cs.stripe_list = g.d_list;
-    const int rc = hec::launch_reconstruct_crc(a, cs, c->device, stream);
-    if (rc <= 0) return rc;
-    return to_status(rc);
+    recon_fused_args(x, g, &a, &cs);
+    return fused_status(hec::launch_reconstruct_crc(a, cs, x.c->device, x.stream));
 }
 
-// Composition, first and last step: the survivors of a group verified
-// (verify = true) or its rebuilt units, read back from d_out, checksummed.
-int recon_crc_sums_pass(hec_coder* c, int kind, bool verify, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                        const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
-                        size_t cell_len, size_t bpc, const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums,
-                        hipStream_t stream) {
-    const size_t k = c->k, n = c->k + c->m;
-    const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    size_t strides[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    uint8_t sid[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    size_t cnt = 0;
-    if (verify) {
-        for (size_t r = 0; r < k; r++, cnt++) {
-            const size_t u = g.rp->plan->rec_survivors[r];
-            bases[cnt] = d_shards[u];
-            strides[cnt] = shard_strides[u];
-            sid[cnt] = uint8_t(u);
-        }
-        return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, nullptr, d_expected,
-                               d_bad, stream, g.d_list);
-    }
-    for (size_t r = 0; r < g.rp->rows.size(); r++) {
-        const size_t u = g.rp->unit(r);
-        bases[cnt] = d_out[u];
-        strides[cnt] = out_strides[u];
-        sid[cnt++] = uint8_t(u);
-    }
-    return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, d_sums, nullptr, nullptr,
-                           stream, g.d_list);
+// A checksum launch over units of a group's stripes: verified against
+// x.d_expected (`verify`), or their sums written to x.d_sums.
+int sums_launch(const VerifiedCall& x, const CrcGroupCall& g, bool verify, const UnitList& l) {
+    return checksum_launch(x.c, x.kind, l.base, l.stride, l.id, l.cnt, x.n(), x.cell_len, g.stripes, x.bpc,
+                           verify ? nullptr : x.d_sums, verify ? x.d_expected : nullptr, verify ? x.d_bad : nullptr,
+                           x.stream, g.d_list);
+}
+
+// The survivors of a group verified by a checksum launch.
+int verify_survivors(const VerifiedCall& x, const CrcGroupCall& g) {
+    UnitList l;
+    l.cnt = x.k();
+    fill_survivors(*g.rp, l.cnt, x.shards(), l.slots());
+    return sums_launch(x, g, true, l);
+}
+
+// Composition, last step: the rebuilt units of a group, read back from d_out,
+// checksummed.
+int recon_crc_sums_pass(const VerifiedCall& x, const CrcGroupCall& g) {
+    UnitList l;
+    for (l.cnt = 0; l.cnt < g.rp->rows.size(); l.cnt++) fill_unit(g.rp->unit(l.cnt), l.cnt, x.outs(), l.slots());
+    return sums_launch(x, g, false, l);
 }
 
 }  // namespace
+
+extern "C" {
 
 int hec_reconstruct_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* const* d_shards,
                                const size_t* shard_strides, uint8_t* const* d_out, const size_t* out_strides,
@@ -2771,37 +2880,35 @@ int hec_reconstruct_crc_device(hec_coder_t* c, int checksum_type, const uint8_t*
                                const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_device");
     int kind;
-    const int chk = recon_crc_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    const int chk = recon_crc_check(c, checksum_type, true, cell_len, bytes_per_checksum, &kind);
     if (chk != HEC_OK) return chk;
     if (kind < 0)
         return hec_reconstruct_device(c, d_shards, shard_strides, d_out, out_strides, want, cell_len, stripes,
                                       hip_stream);
-    if (!d_shards || !shard_strides) return HEC_ERR_INVALID_ARG;
+    if (recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK || !d_shards || !shard_strides)
+        return HEC_ERR_INVALID_ARG;
     return guarded([&]() -> int {
         RowPlan rp;
         const int prc = resolve_reconstruct(c, d_shards, want, d_out, d_out && out_strides, stripes == 0, &rp);
         if (prc != HEC_OK || rp.rows.empty()) return prc;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
         const CrcGroupCall call{&rp, stripes, nullptr};
-        if (recon_crc_shape(c, cell_len, bytes_per_checksum) &&
-            recon_crc_group_aligned(c, call, d_shards, shard_strides, d_out, out_strides)) {
-            const int rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len,
-                                           d_expected, d_bad, d_sums, stream);
+        if (recon_crc_shape(c, cell_len, bytes_per_checksum) && recon_crc_group_aligned(x, call)) {
+            const int rc = recon_crc_fused(x, call);
             if (rc != -1) return rc;  // -1: refused, nothing launched
         }
         // the composition: verify the survivors, rebuild, checksum what was rebuilt
         if (d_expected) {
-            const int rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides,
-                                               cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+            const int rc = verify_survivors(x, call);
             if (rc != HEC_OK) return rc;
         }
         const int rc = hec_reconstruct_device(c, d_shards, shard_strides, d_out, out_strides, want, cell_len, stripes,
                                               hip_stream);
         if (rc != HEC_OK) return rc;
-        return recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
-                                   bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+        return recon_crc_sums_pass(x, call);
     });
 }
 
@@ -2817,12 +2924,13 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
                                      uint8_t* d_sums, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_device_mixed");
     int kind;
-    const int chk = recon_crc_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
+    const int chk = recon_crc_check(c, checksum_type, true, cell_len, bytes_per_checksum, &kind);
     if (chk != HEC_OK) return chk;
     if (kind < 0)
         return hec_reconstruct_device_mixed(c, d_shards, shard_strides, d_out, out_strides, present, want, cell_len,
                                             stripes, d_workspace, workspace_bytes, hip_stream);
-    if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
+    if (recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK || !d_shards || !shard_strides || !present)
+        return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
     for (size_t i = 0; i < c->k + c->m; i++)
@@ -2846,24 +2954,24 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
         if (!d_workspace || (reinterpret_cast<uintptr_t>(d_workspace) & 3u) || workspace_bytes < lists_pos + lists_bytes)
             return HEC_ERR_INVALID_ARG;
         uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
+        const VerifiedCall x{c, kind, d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
         std::vector<CrcGroupCall> calls(batch.plans.size());
         bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum);
         for (size_t gi = 0; gi < calls.size(); gi++) {
             calls[gi] = CrcGroupCall{&batch.plans[gi], off[gi + 1] - off[gi],
                                      reinterpret_cast<const uint32_t*>(d_lists) + off[gi]};
-            fused = fused && recon_crc_group_aligned(c, calls[gi], d_shards, shard_strides, d_out, out_strides);
+            fused = fused && recon_crc_group_aligned(x, calls[gi]);
         }
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+        rc = upload_pinned(c, lists_bytes, d_lists, x.stream,
                            [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
         if (rc != HEC_OK) return rc;
         // 3. one launch per pair ...
         if (fused) {
             for (const CrcGroupCall& call : calls) {
-                rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len, d_expected,
-                                     d_bad, d_sums, stream);
+                rc = recon_crc_fused(x, call);
                 if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
             }
             return HEC_OK;
@@ -2871,16 +2979,14 @@ int hec_reconstruct_crc_device_mixed(hec_coder_t* c, int checksum_type, const ui
         // ... or the composition: verify per pair, one plain mixed call, sums per pair
         if (d_expected)
             for (const CrcGroupCall& call : calls) {
-                rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides, cell_len,
-                                         bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                rc = verify_survivors(x, call);
                 if (rc != HEC_OK) return rc;
             }
         rc = mixed_reconstruct_impl(c, d_shards, shard_strides, d_out, out_strides, present, want, cell_len, stripes,
                                     d_workspace, lists_pos, hip_stream);
         if (rc != HEC_OK) return rc;
         for (const CrcGroupCall& call : calls) {
-            rc = recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
-                                     bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+            rc = recon_crc_sums_pass(x, call);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
@@ -2902,135 +3008,63 @@ struct SumsLens {
     size_t stripe0 = 0;             // the stripe the lengths describe (the launch is that one stripe)
 };
 
-int recon_sums_check(const hec_coder* c, int checksum_type, size_t cell_len, size_t bpc, const uint8_t* d_expected,
-                     const uint8_t* d_bad, const uint8_t* d_sums, int* kind) {
-    if (!c || cell_len == 0) return HEC_ERR_INVALID_ARG;
-    *kind = crc_kind(checksum_type);  // HEC_CHECKSUM_NULL: nothing to compute
-    if (*kind < 0 || bpc == 0 || !d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
-        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
-        return HEC_ERR_INVALID_ARG;
-    return HEC_OK;
-}
-
 // The fused launch of one group of full stripes.  0 ok, -1 refused by the
 // launcher (nothing launched), else HEC_*.
-int recon_sums_fused(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                     const size_t* shard_strides, size_t cell_len, const uint8_t* d_expected, uint8_t* d_bad,
-                     uint8_t* d_sums, hipStream_t stream) {
-    const size_t k = c->k;
-    const DecodePlan& p = *g.rp->plan;
+int recon_sums_fused(const VerifiedCall& x, const CrcGroupCall& g) {
     hec::MatmulArgs a;
-    std::memset(&a, 0, sizeof(a));
     hec::ReconCrcArgs cs;
-    std::memset(&cs, 0, sizeof(cs));
-    for (size_t r = 0; r < k; r++) {
-        const size_t u = p.rec_survivors[r];
-        a.in[r] = d_shards[u];
-        a.in_stride[r] = shard_strides[u];
-        cs.shard_id[r] = uint8_t(u);
-    }
-    for (size_t j = 0; j < g.rp->rows.size(); j++) {
-        const size_t row = g.rp->rows[j];
-        cs.shard_id[k + j] = uint8_t(p.lost[row]);
-        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-    }
-    a.k = int32_t(k);
-    a.r = int32_t(g.rp->rows.size());
-    a.cell_len = cell_len;
-    a.stripes = g.stripes;
-    cs.sums = d_sums;
-    cs.expected = d_expected;
-    cs.bad = d_bad;
-    cs.n_total = uint32_t(c->k + c->m);
-    cs.kind = kind;
-    cs.stripe_list = g.d_list;
-    const int rc = hec::launch_reconstruct_sums(a, cs, c->device, stream);
-    if (rc <= 0) return rc;
-    return to_status(rc);
+    recon_fused_args(x, g, &a, &cs);
+    return fused_status(hec::launch_reconstruct_sums(a, cs, x.c->device, x.stream));
 }
 
 // The generic route of one group: gf_reconstruct_sums_bytes over the group's
 // rows, four per launch.  Full cells (lens.len == nullptr): the survivors are
 // verified by a checksum launch first.  A short last stripe: that one stripe,
 // every unit at its own length, the survivors verified by the same kernel.
-int recon_sums_generic(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                       const size_t* shard_strides, size_t cell_len, size_t bpc, const SumsLens& lens,
-                       const uint8_t* d_expected, uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
-    const size_t k = c->k, n = c->k + c->m;
-    const DecodePlan& p = *g.rp->plan;
-    if (d_expected && !lens.len) {
-        const uint8_t* bases[HEC_MAX_DATA_UNITS];
-        size_t strides[HEC_MAX_DATA_UNITS];
-        uint8_t sid[HEC_MAX_DATA_UNITS];
-        for (size_t r = 0; r < k; r++) {
-            const size_t u = p.rec_survivors[r];
-            bases[r] = d_shards[u];
-            strides[r] = shard_strides[u];
-            sid[r] = uint8_t(u);
-        }
-        const int rc = checksum_launch(c, kind, bases, strides, sid, k, n, cell_len, g.stripes, bpc, nullptr,
-                                       d_expected, d_bad, stream, g.d_list);
+int recon_sums_generic(const VerifiedCall& x, const CrcGroupCall& g, const SumsLens& lens) {
+    const size_t k = x.k();
+    if (x.d_expected && !lens.len) {
+        const int rc = verify_survivors(x, g);
         if (rc != HEC_OK) return rc;
     }
     hec::ReconSumsArgs a;
     std::memset(&a, 0, sizeof(a));
-    for (size_t r = 0; r < k; r++) {
-        const size_t u = p.rec_survivors[r];
-        a.in[r] = d_shards[u];
-        a.in_stride[r] = shard_strides[u];
-        a.in_len[r] = lens.len ? lens.len[u] : cell_len;
-        a.in_id[r] = uint8_t(u);
-    }
+    fill_survivors(*g.rp, k, x.shards(), unit_slots(a.in, a.in_stride, a.in_id));
+    for (size_t r = 0; r < k; r++) a.in_len[r] = lens.len ? lens.len[a.in_id[r]] : x.cell_len;
     a.k = int32_t(k);
-    a.sums = d_sums;
-    a.n_total = uint32_t(n);
-    a.kind = kind;
+    a.sums = x.d_sums;
+    a.n_total = uint32_t(x.n());
+    a.kind = x.kind;
     a.stripe_list = g.d_list;
     a.stripe0 = lens.stripe0;
     a.stripes = g.stripes;
-    a.bytes_per_checksum = bpc;
-    a.nck = cell_len / bpc + (cell_len % bpc != 0);
-    if (lens.len) {  // the first launch also verifies
-        a.expected = d_expected;
-        a.bad = d_bad;
-    }
-    for (size_t j0 = 0; j0 < g.rp->rows.size(); j0 += size_t(hec::kMaxR)) {
-        const size_t rn = std::min(size_t(hec::kMaxR), g.rp->rows.size() - j0);
-        std::memset(a.coef, 0, sizeof(a.coef));
-        for (size_t j = 0; j < rn; j++) {
-            const size_t row = g.rp->rows[j0 + j], u = p.lost[row];
-            a.out_id[j] = uint8_t(u);
-            a.out_len[j] = lens.len ? lens.len[u] : cell_len;
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-        }
-        a.r = int32_t(rn);
-        const int rc = hec::launch_reconstruct_sums_bytes(a, c->device, stream);
-        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
-        a.expected = nullptr;
-        a.bad = nullptr;
-    }
-    return HEC_OK;
+    a.bytes_per_checksum = x.bpc;
+    a.nck = x.cell_len / x.bpc + (x.cell_len % x.bpc != 0);
+    return byte_route_rows(
+        g.rp->rows.size(), false,
+        [&](size_t j0, size_t rn) {
+            std::memset(a.coef, 0, sizeof(a.coef));
+            fill_rows(*g.rp, k, j0, rn, a.coef, x.outs(), id_slots(a.out_id));
+            for (size_t j = 0; j < rn; j++) a.out_len[j] = lens.len ? lens.len[a.out_id[j]] : x.cell_len;
+            a.r = int32_t(rn);
+            // a short stripe: the first launch also verifies
+            a.expected = lens.len && j0 == 0 ? x.d_expected : nullptr;
+            a.bad = lens.len && j0 == 0 ? x.d_bad : nullptr;
+        },
+        [&] { return hec::launch_reconstruct_sums_bytes(a, x.c->device, x.stream); });
 }
 
 // Full stripes of one group: the fused kernel where it takes the shape, else
 // the generic route.
-int recon_sums_group(hec_coder* c, int kind, const CrcGroupCall& g, const uint8_t* const* d_shards,
-                     const size_t* shard_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected,
-                     uint8_t* d_bad, uint8_t* d_sums, hipStream_t stream) {
+int recon_sums_group(const VerifiedCall& x, const CrcGroupCall& g) {
     if (g.stripes == 0) return HEC_OK;
-    bool fused = recon_crc_shape(c, cell_len, bpc) && g.rp->rows.size() <= size_t(hec::kMaxR);
-    if (fused) {
-        uint64_t survivors = 0;
-        for (size_t r = 0; r < c->k; r++) survivors |= uint64_t(1) << g.rp->plan->rec_survivors[r];
-        fused = aligned16(d_shards, shard_strides, survivors);
-    }
-    if (fused) {
-        const int rc = recon_sums_fused(c, kind, g, d_shards, shard_strides, cell_len, d_expected, d_bad, d_sums, stream);
+    if (recon_crc_shape(x.c, x.cell_len, x.bpc) && recon_crc_group_aligned(x, g)) {
+        const int rc = recon_sums_fused(x, g);
         if (rc != -1) return rc;  // -1: refused, nothing launched
     }
-    return recon_sums_generic(c, kind, g, d_shards, shard_strides, cell_len, bpc, SumsLens{}, d_expected, d_bad,
-                              d_sums, stream);
+    return recon_sums_generic(x, g, SumsLens{});
 }
+
 
 }  // namespace
 
@@ -3042,8 +3076,9 @@ int hec_reconstruct_sums_device(hec_coder_t* c, int checksum_type, const uint8_t
                                 uint8_t* d_bad, uint8_t* d_sums, void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_sums_device");
     int kind;
-    const int chk = recon_sums_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
-    if (chk != HEC_OK) return chk;
+    if (recon_crc_check(c, checksum_type, false, cell_len, bytes_per_checksum, &kind) != HEC_OK ||
+        recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK)
+        return HEC_ERR_INVALID_ARG;
     hec::crc::Geometry geo;
     if (!d_shards || !shard_strides ||
         !hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
@@ -3063,16 +3098,13 @@ int hec_reconstruct_sums_device(hec_coder_t* c, int checksum_type, const uint8_t
         if (rp.plan->rec_status != HEC_OK) return rp.plan->rec_status;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
         // only the last stripe can be short: the others as one group of full cells
         const bool short_last = geo.last_len < uint64_t(c->k) * cell_len;
-        const CrcGroupCall full{&rp, short_last ? stripes - 1 : stripes, nullptr};
-        int rc = recon_sums_group(c, kind, full, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
-                                  d_bad, d_sums, stream);
+        const int rc = recon_sums_group(x, CrcGroupCall{&rp, short_last ? stripes - 1 : stripes, nullptr});
         if (rc != HEC_OK || !short_last) return rc;
-        const CrcGroupCall last{&rp, 1, nullptr};
-        return recon_sums_generic(c, kind, last, d_shards, shard_strides, cell_len, bytes_per_checksum,
-                                  SumsLens{geo.len_last, stripes - 1}, d_expected, d_bad, d_sums, stream);
+        return recon_sums_generic(x, CrcGroupCall{&rp, 1, nullptr}, SumsLens{geo.len_last, stripes - 1});
     });
 }
 
@@ -3083,8 +3115,9 @@ int hec_reconstruct_sums_device_mixed(hec_coder_t* c, int checksum_type, const u
                                       size_t workspace_bytes, void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_sums_device_mixed");
     int kind;
-    const int chk = recon_sums_check(c, checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, &kind);
-    if (chk != HEC_OK) return chk;
+    if (recon_crc_check(c, checksum_type, false, cell_len, bytes_per_checksum, &kind) != HEC_OK ||
+        recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK)
+        return HEC_ERR_INVALID_ARG;
     if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
@@ -3114,16 +3147,16 @@ int hec_reconstruct_sums_device_mixed(hec_coder_t* c, int checksum_type, const u
         uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
+        rc = upload_pinned(c, lists_bytes, d_lists, x.stream,
                            [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
         if (rc != HEC_OK) return rc;
         // one launch per pair (more where a pair has over four rows or runs the generic route)
         for (size_t gi = 0; gi < batch.plans.size(); gi++) {
             const CrcGroupCall call{&batch.plans[gi], off[gi + 1] - off[gi],
                                     reinterpret_cast<const uint32_t*>(d_lists) + off[gi]};
-            rc = recon_sums_group(c, kind, call, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
-                                  d_bad, d_sums, stream);
+            rc = recon_sums_group(x, call);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
@@ -3148,95 +3181,49 @@ int recon_rows_check(const hec_coder* c, int checksum_type, size_t cell_len, siz
     return HEC_OK;
 }
 
-int recon_rows_buffers_check(const uint8_t* d_expected, const uint8_t* d_bad, const uint8_t* d_sums) {
-    if (!d_sums || (reinterpret_cast<uintptr_t>(d_sums) & 3u) || (d_expected && !d_bad) ||
-        (reinterpret_cast<uintptr_t>(d_expected) & 3u))
-        return HEC_ERR_INVALID_ARG;
-    return HEC_OK;
-}
-
 // The short stripes of one group (g.stripes of them, g.d_list or lens.stripe0
 // on): gf_reconstruct_crc_rows where `fused` and the launcher takes it, else
 // gf_reconstruct_rows_bytes over the group's rows, four per launch, the first
 // launch verifying the survivors.
-int recon_rows_short(hec_coder* c, int kind, const CrcGroupCall& g, const hec::ReconRowsLens& lens, bool fused,
-                     const uint8_t* const* d_shards, const size_t* shard_strides, uint8_t* const* d_out,
-                     const size_t* out_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected, uint8_t* d_bad,
-                     uint8_t* d_sums, hipStream_t stream) {
+int recon_rows_short(const VerifiedCall& x, const CrcGroupCall& g, const hec::ReconRowsLens& lens, bool fused) {
     if (g.stripes == 0) return HEC_OK;
-    const size_t k = c->k, n = c->k + c->m;
-    const DecodePlan& p = *g.rp->plan;
+    const size_t k = x.k();
     if (fused) {
         hec::MatmulArgs a;
-        std::memset(&a, 0, sizeof(a));
         hec::ReconCrcArgs cs;
-        std::memset(&cs, 0, sizeof(cs));
-        for (size_t r = 0; r < k; r++) {
-            const size_t u = p.rec_survivors[r];
-            a.in[r] = d_shards[u];
-            a.in_stride[r] = shard_strides[u];
-            cs.shard_id[r] = uint8_t(u);
-        }
-        for (size_t j = 0; j < g.rp->rows.size(); j++) {
-            const size_t row = g.rp->rows[j], u = p.lost[row];
-            a.out[j] = d_out[u];
-            a.out_stride[j] = out_strides[u];
-            cs.shard_id[k + j] = uint8_t(u);
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-        }
-        a.k = int32_t(k);
-        a.r = int32_t(g.rp->rows.size());
-        a.cell_len = cell_len;
-        a.stripes = g.stripes;
-        cs.sums = d_sums;
-        cs.expected = d_expected;
-        cs.bad = d_bad;
-        cs.n_total = uint32_t(n);
-        cs.kind = kind;
-        cs.stripe_list = g.d_list;
-        const int rc = hec::launch_reconstruct_crc_rows(a, cs, lens, c->device, stream);
-        if (rc == 0) return HEC_OK;
-        if (rc > 0) return to_status(rc);
-        // -1: refused, nothing launched
+        recon_fused_args(x, g, &a, &cs);
+        const int rc = fused_status(hec::launch_reconstruct_crc_rows(a, cs, lens, x.c->device, x.stream));
+        if (rc != -1) return rc;  // -1: refused, nothing launched
     }
     hec::ReconRowsBytesArgs a;
     std::memset(&a, 0, sizeof(a));
-    for (size_t r = 0; r < k; r++) {
-        const size_t u = p.rec_survivors[r];
-        a.in[r] = d_shards[u];
-        a.in_stride[r] = shard_strides[u];
-        a.in_id[r] = uint8_t(u);
-    }
+    fill_survivors(*g.rp, k, x.shards(), unit_slots(a.in, a.in_stride, a.in_id));
     a.k = int32_t(k);
     a.data_units = uint32_t(k);
-    a.n_total = uint32_t(n);
-    a.sums = d_sums;
-    a.expected = d_expected;
-    a.bad = d_bad;
-    a.kind = kind;
+    a.n_total = uint32_t(x.n());
+    a.sums = x.d_sums;
+    a.expected = x.d_expected;
+    a.bad = x.d_bad;
+    a.kind = x.kind;
     a.stripe_list = g.d_list;
     a.stripes = g.stripes;
     a.lens = lens;
-    a.cell_len = cell_len;
-    a.bytes_per_checksum = bpc;
-    for (size_t j0 = 0; j0 < g.rp->rows.size(); j0 += size_t(hec::kMaxR)) {
-        const size_t rn = std::min(size_t(hec::kMaxR), g.rp->rows.size() - j0);
-        std::memset(a.coef, 0, sizeof(a.coef));
-        for (size_t j = 0; j < rn; j++) {
-            const size_t row = g.rp->rows[j0 + j], u = p.lost[row];
-            a.out[j] = d_out[u];
-            a.out_stride[j] = out_strides[u];
-            a.out_id[j] = uint8_t(u);
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-        }
-        a.r = int32_t(rn);
-        const int rc = hec::launch_reconstruct_rows_bytes(a, c->device, stream);
-        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
-        a.expected = nullptr;  // the survivors are verified once
-        a.bad = nullptr;
-    }
-    return HEC_OK;
+    a.cell_len = x.cell_len;
+    a.bytes_per_checksum = x.bpc;
+    return byte_route_rows(
+        g.rp->rows.size(), false,
+        [&](size_t j0, size_t rn) {
+            std::memset(a.coef, 0, sizeof(a.coef));
+            fill_rows(*g.rp, k, j0, rn, a.coef, x.outs(), unit_slots(a.out, a.out_stride, a.out_id));
+            a.r = int32_t(rn);
+            if (j0 != 0) {  // the survivors are verified once
+                a.expected = nullptr;
+                a.bad = nullptr;
+            }
+        },
+        [&] { return hec::launch_reconstruct_rows_bytes(a, x.c->device, x.stream); });
 }
+
 
 }  // namespace
 
@@ -3254,7 +3241,7 @@ int hec_reconstruct_crc_rows_device(hec_coder_t* c, int checksum_type, const uin
     if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
         return HEC_ERR_INVALID_ARG;
     if (c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_rows_device");
-    if (recon_rows_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    if (recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
     // every stripe full: the existing call, launch for launch
     if (stripes == 0 || geo.last_len == uint64_t(c->k) * cell_len)
         return hec_reconstruct_crc_device(c, checksum_type, d_shards, shard_strides, d_out, out_strides, want, cell_len,
@@ -3273,12 +3260,11 @@ int hec_reconstruct_crc_rows_device(hec_coder_t* c, int checksum_type, const uin
         }
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
         const CrcGroupCall last{&rp, 1, nullptr};
-        const bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum) &&
-                           recon_crc_group_aligned(c, last, d_shards, shard_strides, d_out, out_strides);
-        return recon_rows_short(c, kind, last, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused, d_shards,
-                                shard_strides, d_out, out_strides, cell_len, bytes_per_checksum, d_expected, d_bad,
-                                d_sums, static_cast<hipStream_t>(hip_stream));
+        const bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum) && recon_crc_group_aligned(x, last);
+        return recon_rows_short(x, last, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused);
     });
 }
 
@@ -3300,7 +3286,7 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
     for (size_t s = 0; stripe_bytes && s < stripes; s++)
         if (stripe_bytes[s] > uint64_t(c->k) * cell_len) return HEC_ERR_INVALID_ARG;
     if (c->device == HEC_DEVICE_HOST) return host_only("hec_reconstruct_crc_rows_device_mixed");
-    if (recon_rows_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
+    if (recon_sums_buffers_check(d_expected, d_bad, d_sums) != HEC_OK) return HEC_ERR_INVALID_ARG;
     if (!d_shards || !shard_strides || !present) return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
@@ -3327,6 +3313,8 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
         const uint32_t* d_short = reinterpret_cast<const uint32_t*>(ws + w.short_pos);
         const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
         const size_t plans = batch.plans.size();
+        const VerifiedCall x{c, kind, d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, d_sums, static_cast<hipStream_t>(hip_stream)};
         std::vector<CrcGroupCall> full(plans), shrt(plans);
         bool fused = recon_crc_shape(c, cell_len, bytes_per_checksum);
         for (size_t gi = 0; gi < plans; gi++) {
@@ -3334,12 +3322,11 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
                                     d_full + lists.full_off[gi]};
             shrt[gi] = CrcGroupCall{&batch.plans[gi], lists.short_off[gi + 1] - lists.short_off[gi],
                                     d_short + lists.short_off[gi]};
-            fused = fused && recon_crc_group_aligned(c, full[gi], d_shards, shard_strides, d_out, out_strides);
+            fused = fused && recon_crc_group_aligned(x, full[gi]);
         }
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, stream,
+        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, x.stream,
                            [&](uint8_t* host) { write_rows_image(host, lists, w); });
         if (rc != HEC_OK) return rc;
         // 3. the full stripes as hec_reconstruct_crc_device_mixed runs them:
@@ -3347,8 +3334,7 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
         if (fused) {
             for (const CrcGroupCall& call : full) {
                 if (call.stripes == 0) continue;
-                rc = recon_crc_fused(c, kind, call, d_shards, shard_strides, d_out, out_strides, cell_len, d_expected,
-                                     d_bad, d_sums, stream);
+                rc = recon_crc_fused(x, call);
                 if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
             }
         } else if (!lists.full.empty()) {
@@ -3357,8 +3343,7 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
             if (d_expected)
                 for (const CrcGroupCall& call : full) {
                     if (call.stripes == 0) continue;
-                    rc = recon_crc_sums_pass(c, kind, true, call, d_shards, shard_strides, d_out, out_strides,
-                                             cell_len, bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                    rc = verify_survivors(x, call);
                     if (rc != HEC_OK) return rc;
                 }
             std::vector<uint64_t> want_full;
@@ -3373,16 +3358,13 @@ int hec_reconstruct_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, con
             if (rc != HEC_OK) return rc;
             for (const CrcGroupCall& call : full) {
                 if (call.stripes == 0) continue;
-                rc = recon_crc_sums_pass(c, kind, false, call, d_shards, shard_strides, d_out, out_strides, cell_len,
-                                         bytes_per_checksum, d_expected, d_bad, d_sums, stream);
+                rc = recon_crc_sums_pass(x, call);
                 if (rc != HEC_OK) return rc;
             }
         }
         // 4. one launch per pair over its short stripes
         for (size_t gi = 0; gi < plans; gi++) {
-            rc = recon_rows_short(c, kind, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused,
-                                  d_shards, shard_strides, d_out, out_strides, cell_len, bytes_per_checksum,
-                                  d_expected, d_bad, d_sums, stream);
+            rc = recon_rows_short(x, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
@@ -3403,15 +3385,22 @@ size_t scrub_crc_workspace(size_t k, size_t m, size_t stripes) {
     return align_up(scrub_workspace(k, m, stripes)) + align_up(stripes * sizeof(uint32_t));
 }
 
-// What both entry points check the same way; kind < 0 = HEC_CHECKSUM_NULL.
-int scrub_crc_check(const hec_coder* c, int checksum_type, const uint8_t* const* d_shards, const size_t* shard_strides,
-                    size_t cell_len, size_t stripes, size_t bpc, const uint8_t* d_expected, const uint8_t* d_bad,
-                    const hec_scrub_result_t* d_results, int* kind) {
-    if (!c || !d_shards || !shard_strides || cell_len == 0 || bpc == 0 || !d_results ||
-        (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0 || stripes > SIZE_MAX / sizeof(hec_scrub_result_t))
+// What both entry points check the same way, in two halves (every failure is
+// HEC_ERR_INVALID_ARG): the units' storage and the results array ...
+int scrub_crc_buffers_check(const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides,
+                            size_t stripes, const hec_scrub_result_t* d_results) {
+    if (!c || !d_shards || !shard_strides || !d_results || (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0 ||
+        stripes > SIZE_MAX / sizeof(hec_scrub_result_t))
         return HEC_ERR_INVALID_ARG;
     for (size_t i = 0; i < c->k + c->m; i++)
         if (!d_shards[i]) return HEC_ERR_INVALID_ARG;
+    return HEC_OK;
+}
+
+// ... and the sizes and the checksum; kind < 0 = HEC_CHECKSUM_NULL.
+int scrub_crc_sums_check(int checksum_type, size_t cell_len, size_t bpc, const uint8_t* d_expected,
+                         const uint8_t* d_bad, int* kind) {
+    if (cell_len == 0 || bpc == 0) return HEC_ERR_INVALID_ARG;
     *kind = -1;
     if (checksum_type == HEC_CHECKSUM_NULL) return HEC_OK;
     *kind = crc_kind(checksum_type);
@@ -3423,14 +3412,13 @@ int scrub_crc_check(const hec_coder* c, int checksum_type, const uint8_t* const*
 // The shapes gf_scrub_crc takes (launch_scrub_crc checks the same): k, 512-B
 // chunks, 16-B aligned cells, tile indices in 32 bits (counted in its smaller
 // block tile, 16 KiB).  The extras and row 0 of every plan are checked per plan.
-bool scrub_crc_shape(const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
-                     size_t stripes, size_t bpc) {
-    if (!register_kernel_k(c->k) || bpc != 512 || cell_len % 16 != 0 || cell_len / 16 > 0xFFFFFFFFull ||
+bool scrub_crc_shape(const VerifiedCall& x, size_t stripes) {
+    if (!register_kernel_k(x.k()) || x.bpc != 512 || x.cell_len % 16 != 0 || x.cell_len / 16 > 0xFFFFFFFFull ||
         stripes > 0xFFFFFFFFull)
         return false;
-    const uint64_t tiles = (uint64_t(cell_len) + 16383) / 16384;
+    const uint64_t tiles = (uint64_t(x.cell_len) + 16383) / 16384;
     if (tiles > 0xFFFFFFFFull / stripes) return false;
-    return aligned16(d_shards, shard_strides, unit_bits(c->k + c->m));
+    return aligned16(x.d_shards, x.shard_strides, unit_bits(x.n()));
 }
 
 // At most kMaxR extras and no zero in row 0 of G (the minors divide by it).
@@ -3442,76 +3430,43 @@ bool scrub_crc_plan_fits(const hec_coder* c, const RowPlan& sp) {
     return pivots;
 }
 
-// One group of stripes that share a presence mask: its check plan (null: e ==
-// 0, sums only) and (mixed form) the device list of its stripes.
-struct ScrubCrcGroup {
-    uint64_t mask;
-    const RowPlan* sp;
-    size_t stripes;          // stripes of the group (entries of d_list)
-    const uint32_t* d_list;  // null: stripes 0 .. stripes-1
-};
-
 // The fused launch of one group; with `lens`, of its short stripes
 // (gf_scrub_crc_rows).  0 ok, -1 refused by the launcher, else HEC_*.
-int scrub_crc_fused(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_t* const* d_shards,
-                    const size_t* shard_strides, size_t cell_len, const uint8_t* d_expected, uint8_t* d_bad,
-                    hec_scrub_result_t* d_results, hipStream_t stream, const hec::ReconRowsLens* lens = nullptr) {
-    const size_t k = c->k, n = c->k + c->m;
-    const DecodePlan& p = *g.sp->plan;
+int scrub_crc_fused(const VerifiedCall& x, const CrcGroupCall& g, hec_scrub_result_t* d_results,
+                    const hec::ReconRowsLens* lens = nullptr) {
+    const size_t k = x.k(), r = g.rp->rows.size();
     hec::MatmulArgs a;
     std::memset(&a, 0, sizeof(a));
     hec::ScrubCrcArgs cs;
     std::memset(&cs, 0, sizeof(cs));
-    for (size_t r = 0; r < k; r++) {
-        const size_t u = p.rec_survivors[r];
-        a.in[r] = d_shards[u];
-        a.in_stride[r] = shard_strides[u];
-        cs.shard_id[r] = uint8_t(u);
-    }
-    for (size_t j = 0; j < g.sp->rows.size(); j++) {
-        const size_t row = g.sp->rows[j], u = p.lost[row];
-        a.in[k + j] = d_shards[u];
-        a.in_stride[k + j] = shard_strides[u];
-        cs.shard_id[k + j] = uint8_t(u);
-        for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-    }
+    fill_survivors(*g.rp, k, x.shards(), unit_slots(a.in, a.in_stride, cs.shard_id));
+    fill_rows(*g.rp, k, 0, r, a.coef, x.shards(), unit_slots(a.in + k, a.in_stride + k, cs.shard_id + k));
     a.k = int32_t(k);
-    a.r = int32_t(g.sp->rows.size());
-    a.cell_len = cell_len;
+    a.r = int32_t(r);
+    a.cell_len = x.cell_len;
     a.stripes = g.stripes;
-    cs.expected = d_expected;
-    cs.bad = d_bad;
+    cs.expected = x.d_expected;
+    cs.bad = x.d_bad;
     cs.results = reinterpret_cast<uint64_t*>(d_results);
-    cs.missing = g.sp->missing;
-    cs.n_total = uint32_t(n);
-    cs.kind = kind;
+    cs.missing = g.rp->missing;
+    cs.n_total = uint32_t(x.n());
+    cs.kind = x.kind;
     cs.stripe_list = g.d_list;
-    const int rc = lens ? hec::launch_scrub_crc_rows(a, cs, *lens, c->device, stream)
-                        : hec::launch_scrub_crc(a, cs, c->device, stream);
-    if (rc <= 0) return rc;
-    return to_status(rc);
+    return fused_status(lens ? hec::launch_scrub_crc_rows(a, cs, *lens, x.c->device, x.stream)
+                             : hec::launch_scrub_crc(a, cs, x.c->device, x.stream));
 }
 
 // The present units of a group verified against their sums: the composition's
 // first step, and all there is to do for a group with e == 0.
-int scrub_crc_verify(hec_coder* c, int kind, const ScrubCrcGroup& g, const uint8_t* const* d_shards,
-                     const size_t* shard_strides, size_t cell_len, size_t bpc, const uint8_t* d_expected,
-                     uint8_t* d_bad, hipStream_t stream) {
-    const size_t n = c->k + c->m;
-    const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    size_t strides[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    uint8_t sid[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
-    size_t cnt = 0;
-    for (size_t u = 0; u < n; u++) {
-        if (!((g.mask >> u) & 1)) continue;
-        bases[cnt] = d_shards[u];
-        strides[cnt] = shard_strides[u];
-        sid[cnt++] = uint8_t(u);
-    }
-    if (cnt == 0) return HEC_OK;
-    return checksum_launch(c, kind, bases, strides, sid, cnt, n, cell_len, g.stripes, bpc, nullptr, d_expected, d_bad,
-                           stream, g.d_list);
+int scrub_crc_verify(const VerifiedCall& x, const CrcGroupCall& g) {
+    uint8_t units[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+    UnitList l;
+    l.cnt = mask_units(g.mask & unit_bits(x.n()), units);
+    if (l.cnt == 0) return HEC_OK;
+    fill_units(units, l.cnt, x.shards(), l.slots());
+    return sums_launch(x, g, true, l);
 }
+
 
 }  // namespace
 
@@ -3522,9 +3477,9 @@ int hec_scrub_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* const
                          const uint8_t* d_expected, uint8_t* d_bad, hec_scrub_result_t* d_results, void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_device");
     int kind;
-    const int chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
-                                    d_expected, d_bad, d_results, &kind);
-    if (chk != HEC_OK) return chk;
+    if (scrub_crc_buffers_check(c, d_shards, shard_strides, stripes, d_results) != HEC_OK ||
+        scrub_crc_sums_check(checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, &kind) != HEC_OK)
+        return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
     if (kind < 0) return hec_scrub_device(c, d_shards, shard_strides, cell_len, stripes, d_results, hip_stream);
     return guarded([&]() -> int {
@@ -3535,20 +3490,18 @@ int hec_scrub_crc_device(hec_coder_t* c, int checksum_type, const uint8_t* const
         if (prc != HEC_OK) return prc;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        const ScrubCrcGroup call{all, &sp, stripes, nullptr};
-        if (scrub_crc_plan_fits(c, sp) &&
-            scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum)) {
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
+        const CrcGroupCall call{&sp, stripes, nullptr, all};
+        if (scrub_crc_plan_fits(c, sp) && scrub_crc_shape(x, stripes)) {
             // the kernel only ORs and adds into the words: zeroed here, in
             // stream order (a zeroing kernel node under capture)
-            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
-            const int rc = scrub_crc_fused(c, kind, call, d_shards, shard_strides, cell_len, d_expected, d_bad,
-                                           d_results, stream);
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), x.stream), HEC_ERR_DEVICE);
+            const int rc = scrub_crc_fused(x, call, d_results);
             if (rc != -1) return rc;  // -1: refused, no kernel launched
         }
         // the composition: verify every unit, then the plain scrub (which zeroes the results)
-        const int rc = scrub_crc_verify(c, kind, call, d_shards, shard_strides, cell_len, bytes_per_checksum,
-                                        d_expected, d_bad, stream);
+        const int rc = scrub_crc_verify(x, call);
         if (rc != HEC_OK) return rc;
         return hec_scrub_device(c, d_shards, shard_strides, cell_len, stripes, d_results, hip_stream);
     });
@@ -3566,9 +3519,10 @@ int hec_scrub_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t*
                                void* hip_stream) {
     if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_device_mixed");
     int kind;
-    const int chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
-                                    d_expected, d_bad, d_results, &kind);
-    if (chk != HEC_OK || !present) return chk != HEC_OK ? chk : HEC_ERR_INVALID_ARG;
+    if (scrub_crc_buffers_check(c, d_shards, shard_strides, stripes, d_results) != HEC_OK ||
+        scrub_crc_sums_check(checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, &kind) != HEC_OK ||
+        !present)
+        return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
     if (kind < 0)
@@ -3602,10 +3556,11 @@ int hec_scrub_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t*
             return HEC_ERR_INVALID_ARG;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        const bool fused = fits && scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
+        const bool fused = fits && scrub_crc_shape(x, stripes);
         if (idle || fused)  // the composition's scrub call zeroes them itself
-            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), x.stream), HEC_ERR_DEVICE);
         if (idle) return HEC_OK;
         // 2. the lists, flat -- the plans' and then the bare masks' -- behind
         // the plain mixed call's part of the workspace
@@ -3618,34 +3573,31 @@ int hec_scrub_crc_device_mixed(hec_coder_t* c, int checksum_type, const uint8_t*
         }
         const size_t lists_bytes = flat.size() * sizeof(uint32_t);
         uint8_t* d_lists = static_cast<uint8_t*>(d_workspace) + lists_pos;
-        rc = upload_pinned(c, lists_bytes, d_lists, stream,
+        rc = upload_pinned(c, lists_bytes, d_lists, x.stream,
                            [&](uint8_t* host) { std::memcpy(host, flat.data(), lists_bytes); });
         if (rc != HEC_OK) return rc;
-        std::vector<ScrubCrcGroup> groups;
+        std::vector<CrcGroupCall> groups;
         for (size_t gi = 0; gi < batch.plans.size(); gi++)
-            groups.push_back(ScrubCrcGroup{all & ~batch.plans[gi].missing, &batch.plans[gi], off[gi + 1] - off[gi],
-                                           reinterpret_cast<const uint32_t*>(d_lists) + off[gi]});
+            groups.push_back(CrcGroupCall{&batch.plans[gi], off[gi + 1] - off[gi],
+                                          reinterpret_cast<const uint32_t*>(d_lists) + off[gi],
+                                          all & ~batch.plans[gi].missing});
         size_t gi = batch.plans.size();
         for (const auto& b : bare) {
-            groups.push_back(ScrubCrcGroup{b.first, nullptr, off[gi + 1] - off[gi],
-                                           reinterpret_cast<const uint32_t*>(d_lists) + off[gi]});
+            groups.push_back(CrcGroupCall{nullptr, off[gi + 1] - off[gi],
+                                          reinterpret_cast<const uint32_t*>(d_lists) + off[gi], b.first});
             gi++;
         }
         // 3. one launch per mask: the fused kernel, or sums only where e == 0 ...
         if (fused) {
-            for (const ScrubCrcGroup& grp : groups) {
-                rc = grp.sp ? scrub_crc_fused(c, kind, grp, d_shards, shard_strides, cell_len, d_expected, d_bad,
-                                              d_results, stream)
-                            : scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum,
-                                               d_expected, d_bad, stream);
+            for (const CrcGroupCall& grp : groups) {
+                rc = grp.rp ? scrub_crc_fused(x, grp, d_results) : scrub_crc_verify(x, grp);
                 if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
             }
             return HEC_OK;
         }
         // ... or the composition: verify per mask, then the plain mixed scrub
-        for (const ScrubCrcGroup& grp : groups) {
-            rc = scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
-                                  d_bad, stream);
+        for (const CrcGroupCall& grp : groups) {
+            rc = scrub_crc_verify(x, grp);
             if (rc != HEC_OK) return rc;
         }
         return hec_scrub_device_mixed(c, d_shards, shard_strides, present, cell_len, stripes, d_results, d_workspace,
@@ -3718,72 +3670,55 @@ size_t scrub_rows_workspace(size_t k, size_t m, size_t stripes) {
 }
 
 // The shapes gf_scrub_crc_rows takes: gf_scrub_crc's, with lengths in 32 bits.
-bool scrub_rows_shape(const hec_coder* c, const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
-                      size_t stripes, size_t bpc) {
-    return cell_len <= 0x7FFFFFFFull && scrub_crc_shape(c, d_shards, shard_strides, cell_len, stripes, bpc);
+bool scrub_rows_shape(const VerifiedCall& x, size_t stripes) {
+    return x.cell_len <= 0x7FFFFFFFull && scrub_crc_shape(x, stripes);
 }
 
 // The short stripes of one group (g.stripes of them, g.d_list or lens.stripe0
 // on): gf_scrub_crc_rows where `fused`, the group has a check plan and the
 // launcher takes it, else gf_scrub_rows_bytes (also all there is for a group
 // with e == 0: the units' sums over their own bytes).
-int scrub_rows_short(hec_coder* c, int kind, const ScrubCrcGroup& g, const hec::ReconRowsLens& lens, bool fused,
-                     const uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len, size_t bpc,
-                     const uint8_t* d_expected, uint8_t* d_bad, hec_scrub_result_t* d_results, hipStream_t stream) {
+int scrub_rows_short(const VerifiedCall& x, const CrcGroupCall& g, const hec::ReconRowsLens& lens, bool fused,
+                     hec_scrub_result_t* d_results) {
     if (g.stripes == 0) return HEC_OK;
-    const size_t k = c->k, n = c->k + c->m;
-    if (fused && g.sp) {
-        const int rc = scrub_crc_fused(c, kind, g, d_shards, shard_strides, cell_len, d_expected, d_bad, d_results,
-                                       stream, &lens);
+    const size_t k = x.k();
+    if (fused && g.rp) {
+        const int rc = scrub_crc_fused(x, g, d_results, &lens);
         if (rc != -1) return rc;  // -1: refused, nothing launched
     }
     hec::ScrubRowsBytesArgs a;
     std::memset(&a, 0, sizeof(a));
-    size_t cnt = 0;
-    if (g.sp) {
-        const DecodePlan& p = *g.sp->plan;
-        if (g.sp->rows.size() > size_t(hec::kScrubRowsMaxE)) return HEC_ERR_INVALID_ARG;
-        for (size_t r = 0; r < k; r++) {
-            const size_t u = p.rec_survivors[r];
-            a.in[cnt] = d_shards[u];
-            a.in_stride[cnt] = shard_strides[u];
-            a.id[cnt++] = uint8_t(u);
-        }
+    if (g.rp) {
+        const size_t e = g.rp->rows.size();
+        if (e > size_t(hec::kScrubRowsMaxE)) return HEC_ERR_INVALID_ARG;
+        fill_survivors(*g.rp, k, x.shards(), unit_slots(a.in, a.in_stride, a.id));
+        fill_rows(*g.rp, k, 0, e, a.coef, x.shards(), unit_slots(a.in + k, a.in_stride + k, a.id + k));
         a.ns = int32_t(k);
-        for (size_t j = 0; j < g.sp->rows.size(); j++) {
-            const size_t row = g.sp->rows[j], u = p.lost[row];
-            a.in[cnt] = d_shards[u];
-            a.in_stride[cnt] = shard_strides[u];
-            a.id[cnt++] = uint8_t(u);
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = p.rec_matrix[row * k + i];
-        }
-        a.e = int32_t(g.sp->rows.size());
-        a.missing = g.sp->missing;
+        a.e = int32_t(e);
+        a.missing = g.rp->missing;
     } else {
-        for (size_t u = 0; u < n; u++) {
-            if (!((g.mask >> u) & 1)) continue;
-            a.in[cnt] = d_shards[u];
-            a.in_stride[cnt] = shard_strides[u];
-            a.id[cnt++] = uint8_t(u);
-        }
+        uint8_t units[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
+        const size_t cnt = mask_units(g.mask & unit_bits(x.n()), units);
         if (cnt == 0) return HEC_OK;
+        fill_units(units, cnt, x.shards(), unit_slots(a.in, a.in_stride, a.id));
         a.ns = int32_t(cnt);
     }
     a.data_units = uint32_t(k);
-    a.n_total = uint32_t(n);
-    a.expected = d_expected;
-    a.bad = d_bad;
+    a.n_total = uint32_t(x.n());
+    a.expected = x.d_expected;
+    a.bad = x.d_bad;
     a.results = reinterpret_cast<uint64_t*>(d_results);
-    a.kind = kind;
+    a.kind = x.kind;
     a.stripe_list = g.d_list;
     a.stripes = g.stripes;
     a.lens = lens;
-    a.cell_len = cell_len;
-    a.bytes_per_checksum = bpc;
-    const int rc = hec::launch_scrub_rows_bytes(a, c->device, stream);
+    a.cell_len = x.cell_len;
+    a.bytes_per_checksum = x.bpc;
+    const int rc = hec::launch_scrub_rows_bytes(a, x.c->device, x.stream);
     if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
     return HEC_OK;
 }
+
 
 }  // namespace
 
@@ -3800,9 +3735,9 @@ int hec_scrub_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* 
     if (!hec::crc::make_geometry(c->k + c->m, c->k, cell_len, stripes, bytes_per_checksum, data_len, &geo))
         return HEC_ERR_INVALID_ARG;
     if (c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_rows_device");
-    chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum, d_expected,
-                          d_bad, d_results, &kind);
-    if (chk != HEC_OK) return chk;
+    if (scrub_crc_buffers_check(c, d_shards, shard_strides, stripes, d_results) != HEC_OK ||
+        scrub_crc_sums_check(checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, &kind) != HEC_OK)
+        return HEC_ERR_INVALID_ARG;
     // every stripe full: the existing call, launch for launch
     if (stripes == 0 || geo.last_len == uint64_t(c->k) * cell_len)
         return hec_scrub_crc_device(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum,
@@ -3815,18 +3750,17 @@ int hec_scrub_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* 
         if (prc != HEC_OK) return prc;
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
         const RowPlan* plan = sp.rows.empty() ? nullptr : &sp;
-        bool fused = plan && scrub_crc_plan_fits(c, sp) &&
-                     scrub_rows_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        bool fused = plan && scrub_crc_plan_fits(c, sp) && scrub_rows_shape(x, stripes);
         // one launch over the stripes - 1 full stripes, one over the last;
         // the results are zeroed once, in stream order (a zeroing kernel node
         // under capture)
         if (fused) {
-            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), x.stream), HEC_ERR_DEVICE);
             if (stripes > 1) {
-                const int rc = scrub_crc_fused(c, kind, ScrubCrcGroup{all, plan, stripes - 1, nullptr}, d_shards,
-                                               shard_strides, cell_len, d_expected, d_bad, d_results, stream);
+                const int rc = scrub_crc_fused(x, CrcGroupCall{plan, stripes - 1, nullptr, all}, d_results);
                 if (rc == -1) fused = false;  // refused, no kernel launched
                 else if (rc != HEC_OK) return rc;
             }
@@ -3838,11 +3772,10 @@ int hec_scrub_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* 
                                                     bytes_per_checksum, d_expected, d_bad, d_results, hip_stream);
                 if (rc != HEC_OK) return rc;
             }
-            HEC_HIP(hec::zero_async(d_results + (stripes - 1), sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            HEC_HIP(hec::zero_async(d_results + (stripes - 1), sizeof(hec_scrub_result_t), x.stream), HEC_ERR_DEVICE);
         }
-        return scrub_rows_short(c, kind, ScrubCrcGroup{all, plan, 1, nullptr},
-                                hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused, d_shards, shard_strides,
-                                cell_len, bytes_per_checksum, d_expected, d_bad, d_results, stream);
+        return scrub_rows_short(x, CrcGroupCall{plan, 1, nullptr, all},
+                                hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, fused, d_results);
     });
 }
 
@@ -3866,9 +3799,10 @@ int hec_scrub_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uin
         any_short = any_short || rows_short(stripe_bytes[s], c->k, cell_len);
     }
     if (c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_crc_rows_device_mixed");
-    chk = scrub_crc_check(c, checksum_type, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum, d_expected,
-                          d_bad, d_results, &kind);
-    if (chk != HEC_OK || !present) return chk != HEC_OK ? chk : HEC_ERR_INVALID_ARG;
+    if (scrub_crc_buffers_check(c, d_shards, shard_strides, stripes, d_results) != HEC_OK ||
+        scrub_crc_sums_check(checksum_type, cell_len, bytes_per_checksum, d_expected, d_bad, &kind) != HEC_OK ||
+        !present)
+        return HEC_ERR_INVALID_ARG;
     // every stripe full: the existing call, launch for launch
     if (stripes == 0 || !any_short)
         return hec_scrub_crc_device_mixed(c, checksum_type, d_shards, shard_strides, present, cell_len, stripes,
@@ -3893,46 +3827,43 @@ int hec_scrub_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uin
         const RowsLayout w = scrub_rows_layout(k, m, stripes, lists.full.size(), lists.shrt.size());
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        const bool fused = fits && scrub_rows_shape(c, d_shards, shard_strides, cell_len, stripes, bytes_per_checksum);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
+        const bool fused = fits && scrub_rows_shape(x, stripes);
         const bool composed = !fused && !lists.full.empty();  // the plain mixed scrub zeroes the results itself
         if (!composed)
-            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), stream), HEC_ERR_DEVICE);
+            HEC_HIP(hec::zero_async(d_results, stripes * sizeof(hec_scrub_result_t), x.stream), HEC_ERR_DEVICE);
         if (idle) return HEC_OK;
         uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, stream,
+        rc = upload_pinned(c, w.image_bytes, ws + w.full_pos, x.stream,
                            [&](uint8_t* host) { write_rows_image(host, lists, w); });
         if (rc != HEC_OK) return rc;
         const uint32_t* d_full = reinterpret_cast<const uint32_t*>(ws + w.full_pos);
         const uint32_t* d_short = reinterpret_cast<const uint32_t*>(ws + w.short_pos);
         const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
         const size_t groups = batch.plans.size();
-        std::vector<ScrubCrcGroup> full(groups), shrt(groups);
+        std::vector<CrcGroupCall> full(groups), shrt(groups);
         for (size_t gi = 0; gi < groups; gi++) {
             const RowPlan* sp = batch.plans[gi].rows.empty() ? nullptr : &batch.plans[gi];
             const uint64_t mask = all & ~batch.plans[gi].missing;
-            full[gi] = ScrubCrcGroup{mask, sp, lists.full_off[gi + 1] - lists.full_off[gi], d_full + lists.full_off[gi]};
+            full[gi] = CrcGroupCall{sp, lists.full_off[gi + 1] - lists.full_off[gi], d_full + lists.full_off[gi], mask};
             shrt[gi] =
-                ScrubCrcGroup{mask, sp, lists.short_off[gi + 1] - lists.short_off[gi], d_short + lists.short_off[gi]};
+                CrcGroupCall{sp, lists.short_off[gi + 1] - lists.short_off[gi], d_short + lists.short_off[gi], mask};
         }
         // 3. the full stripes as hec_scrub_crc_device_mixed runs them: one
         // launch per mask, the fused kernel or sums only where e == 0 ...
         if (fused) {
-            for (const ScrubCrcGroup& grp : full) {
+            for (const CrcGroupCall& grp : full) {
                 if (grp.stripes == 0) continue;
-                rc = grp.sp ? scrub_crc_fused(c, kind, grp, d_shards, shard_strides, cell_len, d_expected, d_bad,
-                                              d_results, stream)
-                            : scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum,
-                                               d_expected, d_bad, stream);
+                rc = grp.rp ? scrub_crc_fused(x, grp, d_results) : scrub_crc_verify(x, grp);
                 if (rc != HEC_OK) return rc == -1 ? HEC_ERR_INVALID_ARG : rc;
             }
         } else if (composed) {
             // ... or the composition: verify per mask, then the plain mixed
             // scrub with the short stripes masked out (no unit: unchecked)
-            for (const ScrubCrcGroup& grp : full) {
+            for (const CrcGroupCall& grp : full) {
                 if (grp.stripes == 0) continue;
-                rc = scrub_crc_verify(c, kind, grp, d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected,
-                                      d_bad, stream);
+                rc = scrub_crc_verify(x, grp);
                 if (rc != HEC_OK) return rc;
             }
             std::vector<uint64_t> present_full(stripes);
@@ -3944,9 +3875,8 @@ int hec_scrub_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uin
         }
         // 4. one launch per mask over its short stripes
         for (size_t gi = 0; gi < groups; gi++) {
-            rc = scrub_rows_short(c, kind, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused,
-                                  d_shards, shard_strides, cell_len, bytes_per_checksum, d_expected, d_bad, d_results,
-                                  stream);
+            rc = scrub_rows_short(x, shrt[gi], hec::ReconRowsLens{d_bytes + lists.short_off[gi], 0, 0}, fused,
+                                  d_results);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
@@ -3995,111 +3925,103 @@ int encode_rows_buffers_check(const hec_coder* c, const uint8_t* const* d_data, 
 // `stripes` stripes from batch stripe lens.stripe0 on, lengths in `lens`:
 // gf_encode_crc_rows where the launcher takes the shape, else
 // gf_encode_rows_bytes, four parity rows per launch, the first launch summing
-// the data units.  The caller has checked the buffers.
-int encode_rows_launch(hec_coder* c, int kind, const hec::ReconRowsLens& lens, const uint8_t* const* d_data,
-                       const size_t* data_strides, uint8_t* const* d_parity, const size_t* parity_strides,
-                       size_t cell_len, size_t stripes, size_t bpc, uint8_t* d_sums, hipStream_t stream) {
+// the data units.  The caller has checked the buffers.  The units are the
+// call's own arrays in their order and the rows the coder's parity rows, so
+// the slots are filled here, not from a plan.
+int encode_rows_launch(const VerifiedCall& x, const hec::ReconRowsLens& lens, size_t stripes) {
     if (stripes == 0) return HEC_OK;
-    const size_t k = c->k, m = c->m;
-    if (bpc == 512 && m <= size_t(hec::kMaxR)) {
+    const size_t k = x.k(), m = x.c->m;
+    const uint8_t* enc = x.c->enc.data();
+    if (x.bpc == 512 && m <= size_t(hec::kMaxR)) {
         hec::MatmulArgs a;
         std::memset(&a, 0, sizeof(a));
         for (size_t i = 0; i < k; i++) {
-            a.in[i] = d_data[i];
-            a.in_stride[i] = data_strides[i];
+            a.in[i] = x.d_shards[i];
+            a.in_stride[i] = x.shard_strides[i];
         }
         for (size_t j = 0; j < m; j++) {
-            a.out[j] = d_parity[j];
-            a.out_stride[j] = parity_strides[j];
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = c->enc[(k + j) * k + i];
+            a.out[j] = x.d_out[j];
+            a.out_stride[j] = x.out_strides[j];
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = enc[(k + j) * k + i];
         }
         a.k = int32_t(k);
         a.r = int32_t(m);
-        a.cell_len = cell_len;
+        a.cell_len = x.cell_len;
         a.stripes = stripes;
         hec::EncodeRowsCrcArgs cs;
         std::memset(&cs, 0, sizeof(cs));
-        cs.sums = d_sums;
+        cs.sums = x.d_sums;
         cs.n_total = uint32_t(k + m);
-        cs.kind = kind;
-        const int rc = hec::launch_encode_crc_rows(a, cs, lens, c->device, stream);
-        if (rc == 0) return HEC_OK;
-        if (rc > 0) return to_status(rc);
-        // -1: refused, nothing launched
+        cs.kind = x.kind;
+        const int rc = fused_status(hec::launch_encode_crc_rows(a, cs, lens, x.c->device, x.stream));
+        if (rc != -1) return rc;  // -1: refused, nothing launched
     }
     hec::EncodeRowsBytesArgs a;
     std::memset(&a, 0, sizeof(a));
     for (size_t i = 0; i < k; i++) {
-        a.in[i] = d_data[i];
-        a.in_stride[i] = data_strides[i];
+        a.in[i] = x.d_shards[i];
+        a.in_stride[i] = x.shard_strides[i];
     }
     a.k = int32_t(k);
     a.n_total = uint32_t(k + m);
-    a.sums = d_sums;
-    a.kind = kind;
+    a.sums = x.d_sums;
+    a.kind = x.kind;
     a.stripes = stripes;
     a.lens = lens;
-    a.cell_len = cell_len;
-    a.bytes_per_checksum = bpc;
-    a.data_sums = 1;
-    for (size_t j0 = 0; j0 < m; j0 += size_t(hec::kMaxR)) {
-        const size_t rn = std::min(size_t(hec::kMaxR), m - j0);
-        std::memset(a.coef, 0, sizeof(a.coef));
-        for (size_t j = 0; j < rn; j++) {
-            a.out[j] = d_parity[j0 + j];
-            a.out_stride[j] = parity_strides[j0 + j];
-            a.out_id[j] = uint8_t(k + j0 + j);
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = c->enc[(k + j0 + j) * k + i];
-        }
-        a.r = int32_t(rn);
-        const int rc = hec::launch_encode_rows_bytes(a, c->device, stream);
-        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
-        a.data_sums = 0;  // the data units are summed once
-    }
-    return HEC_OK;
+    a.cell_len = x.cell_len;
+    a.bytes_per_checksum = x.bpc;
+    return byte_route_rows(
+        m, false,
+        [&](size_t j0, size_t rn) {
+            std::memset(a.coef, 0, sizeof(a.coef));
+            for (size_t j = 0; j < rn; j++) {
+                a.out[j] = x.d_out[j0 + j];
+                a.out_stride[j] = x.out_strides[j0 + j];
+                a.out_id[j] = uint8_t(k + j0 + j);
+                for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = enc[(k + j0 + j) * k + i];
+            }
+            a.r = int32_t(rn);
+            a.data_sums = j0 == 0;  // the data units are summed once
+        },
+        [&] { return hec::launch_encode_rows_bytes(a, x.c->device, x.stream); });
 }
 
 // `stripes` full stripes from stripe 0 on.  CRC32C: hec_encode_crc_device.
 // CRC32: gf_encode_crc_rows with every stripe at k * cell_len where it takes
 // the shape, else hec_encode_device, then hec_checksum_device.
-int encode_rows_full(hec_coder* c, int checksum_type, int kind, const uint8_t* const* d_data,
-                     const size_t* data_strides, uint8_t* const* d_parity, const size_t* parity_strides,
-                     size_t cell_len, size_t stripes, size_t bpc, uint8_t* d_sums, void* hip_stream) {
+int encode_rows_full(const VerifiedCall& x, int checksum_type, size_t stripes) {
     if (stripes == 0) return HEC_OK;
-    if (kind == hec::crc::kCrc32c)
-        return hec_encode_crc_device(c, d_data, data_strides, d_parity, parity_strides, cell_len, stripes, bpc, d_sums,
-                                     hip_stream);
+    hec_coder* c = x.c;
+    if (x.kind == hec::crc::kCrc32c)
+        return hec_encode_crc_device(c, x.d_shards, x.shard_strides, x.d_out, x.out_strides, x.cell_len, stripes, x.bpc,
+                                     x.d_sums, x.stream);
     const size_t k = c->k, m = c->m;
-    bool one_pass = bpc == 512 && m <= size_t(hec::kMaxR) && cell_len % 16 == 0 && cell_len <= 0x7FFFFFFFull &&
-                    stripes <= 0xFFFFFFFFull && (k == 2 || k == 3 || k == 6 || k == 10);
-    for (size_t i = 0; i < k; i++)
-        one_pass = one_pass && ((reinterpret_cast<uintptr_t>(d_data[i]) | data_strides[i]) & 15u) == 0;
-    for (size_t j = 0; j < m; j++)
-        one_pass = one_pass && ((reinterpret_cast<uintptr_t>(d_parity[j]) | parity_strides[j]) & 15u) == 0;
-    if (one_pass) {
-        const int rc = guarded([&]() -> int {
+    const bool one_pass = x.bpc == 512 && m <= size_t(hec::kMaxR) && x.cell_len % 16 == 0 &&
+                          x.cell_len <= 0x7FFFFFFFull && stripes <= 0xFFFFFFFFull && register_kernel_k(k) &&
+                          aligned16(x.d_shards, x.shard_strides, unit_bits(k)) &&
+                          aligned16(x.d_out, x.out_strides, unit_bits(m));
+    if (one_pass)
+        return guarded([&]() -> int {
             DeviceGuard g(c->device);
             if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-            return encode_rows_launch(c, kind, hec::ReconRowsLens{nullptr, uint64_t(k) * cell_len, 0}, d_data,
-                                      data_strides, d_parity, parity_strides, cell_len, stripes, bpc, d_sums,
-                                      static_cast<hipStream_t>(hip_stream));
+            return encode_rows_launch(x, hec::ReconRowsLens{nullptr, uint64_t(k) * x.cell_len, 0}, stripes);
         });
-        return rc;
-    }
-    const int rc = hec_encode_device(c, d_data, data_strides, d_parity, parity_strides, cell_len, stripes, hip_stream);
+    const int rc =
+        hec_encode_device(c, x.d_shards, x.shard_strides, x.d_out, x.out_strides, x.cell_len, stripes, x.stream);
     if (rc != HEC_OK) return rc;
     const uint8_t* bases[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
     size_t st[HEC_MAX_DATA_UNITS + HEC_MAX_PARITY_UNITS];
     for (size_t i = 0; i < k; i++) {
-        bases[i] = d_data[i];
-        st[i] = data_strides[i];
+        bases[i] = x.d_shards[i];
+        st[i] = x.shard_strides[i];
     }
     for (size_t j = 0; j < m; j++) {
-        bases[k + j] = d_parity[j];
-        st[k + j] = parity_strides[j];
+        bases[k + j] = x.d_out[j];
+        st[k + j] = x.out_strides[j];
     }
-    return hec_checksum_device(c, checksum_type, bases, st, k + m, cell_len, stripes, bpc, d_sums, hip_stream);
+    return hec_checksum_device(c, checksum_type, bases, st, k + m, x.cell_len, stripes, x.bpc, x.d_sums, x.stream);
 }
+
 
 }  // namespace
 
@@ -4119,21 +4041,18 @@ int hec_encode_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t*
     chk = encode_rows_buffers_check(c, d_data, data_strides, d_parity, parity_strides, d_sums);
     if (chk != HEC_OK) return chk;
     if (stripes == 0) return HEC_OK;
+    const VerifiedCall x{c, kind, d_data, data_strides, d_parity, parity_strides, cell_len, bytes_per_checksum,
+                         nullptr, nullptr, d_sums, static_cast<hipStream_t>(hip_stream)};
     // every stripe full: one call over all of them
-    if (geo.last_len == uint64_t(c->k) * cell_len)
-        return encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
-                                stripes, bytes_per_checksum, d_sums, hip_stream);
+    if (geo.last_len == uint64_t(c->k) * cell_len) return encode_rows_full(x, checksum_type, stripes);
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
     // the stripes - 1 full stripes, then one launch over the last
-    const int rc = encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
-                                    stripes - 1, bytes_per_checksum, d_sums, hip_stream);
+    const int rc = encode_rows_full(x, checksum_type, stripes - 1);
     if (rc != HEC_OK) return rc;
     return guarded([&]() -> int {
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        return encode_rows_launch(c, kind, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, d_data, data_strides,
-                                  d_parity, parity_strides, cell_len, 1, bytes_per_checksum, d_sums,
-                                  static_cast<hipStream_t>(hip_stream));
+        return encode_rows_launch(x, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, 1);
     });
 }
 
@@ -4163,24 +4082,21 @@ int hec_encode_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const ui
                       workspace_bytes < encode_rows_workspace(stripes)))
         return HEC_ERR_INVALID_ARG;
     if (stripes == 0) return HEC_OK;
+    const VerifiedCall x{c, kind, d_data, data_strides, d_parity, parity_strides, cell_len, bytes_per_checksum,
+                         nullptr, nullptr, d_sums, static_cast<hipStream_t>(hip_stream)};
     // no short entry: the uniform form with data_len == 0
-    if (!any_short)
-        return encode_rows_full(c, checksum_type, kind, d_data, data_strides, d_parity, parity_strides, cell_len,
-                                stripes, bytes_per_checksum, d_sums, hip_stream);
+    if (!any_short) return encode_rows_full(x, checksum_type, stripes);
     if (stripes > 0xFFFFFFFFull) return HEC_ERR_INVALID_ARG;
     // one launch over all stripes, full ones included, with the lengths on
     // the device
     return guarded([&]() -> int {
         DeviceGuard g(c->device);
         if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-        const int rc = upload_pinned(c, encode_rows_workspace(stripes), d_workspace, stream, [&](uint8_t* host) {
+        const int rc = upload_pinned(c, encode_rows_workspace(stripes), d_workspace, x.stream, [&](uint8_t* host) {
             write_encode_rows_image(host, stripe_bytes, stripes, c->k, cell_len);
         });
         if (rc != HEC_OK) return rc;
-        return encode_rows_launch(c, kind, hec::ReconRowsLens{static_cast<const uint64_t*>(d_workspace), 0, 0}, d_data,
-                                  data_strides, d_parity, parity_strides, cell_len, stripes, bytes_per_checksum,
-                                  d_sums, stream);
+        return encode_rows_launch(x, hec::ReconRowsLens{static_cast<const uint64_t*>(d_workspace), 0, 0}, stripes);
     });
 }
 
@@ -4313,86 +4229,75 @@ int read_rows_buffers_check(const uint8_t* const* d_shards, const size_t* shard_
 
 // `stripes` stripes of one group (d_list, or lens.stripe0 on): gf_read_rows
 // where the launcher takes the shape, else gf_read_rows_bytes over the lost
-// data units, four per launch, the first launch verifying every survivor and
-// copying the present data units.
-int read_rows_launch(hec_coder* c, int kind, const ReadRowsGroup& g, const uint32_t* d_list, size_t stripes,
-                     const hec::ReconRowsLens& lens, const uint8_t* const* d_shards, const size_t* shard_strides,
-                     uint8_t* d_file, size_t file_stride, size_t cell_len, size_t bpc, const uint8_t* d_expected,
-                     uint8_t* d_bad, hipStream_t stream) {
+// data units, four per launch (one launch where none is lost), the first
+// launch verifying every survivor and copying the present data units.  The
+// rows are those of the decode plan (g.plan->matrix), so they are filled here.
+int read_rows_launch(const VerifiedCall& x, const ReadRowsGroup& g, const uint32_t* d_list, size_t stripes,
+                     const hec::ReconRowsLens& lens, uint8_t* d_file, size_t file_stride) {
     if (stripes == 0) return HEC_OK;
-    const size_t k = c->k, n = c->k + c->m, e = g.lost.size();
-    if (bpc == 512 && e <= size_t(hec::kMaxR)) {
+    const size_t k = x.k(), e = g.lost.size();
+    if (x.bpc == 512 && e <= size_t(hec::kMaxR)) {
         hec::MatmulArgs a;
         std::memset(&a, 0, sizeof(a));
         hec::ReadRowsCrcArgs cs;
         std::memset(&cs, 0, sizeof(cs));
-        for (size_t i = 0; i < k; i++) {
-            const size_t u = g.survivors[i];
-            a.in[i] = d_shards[u];
-            a.in_stride[i] = shard_strides[u];
-            cs.shard_id[i] = uint8_t(u);
-        }
+        fill_units(g.survivors.data(), k, x.shards(), unit_slots(a.in, a.in_stride, cs.shard_id));
         for (size_t j = 0; j < e; j++) {
             cs.shard_id[k + j] = g.lost[j];
             for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = g.plan->matrix[j * k + i];
         }
         a.k = int32_t(k);
         a.r = int32_t(e);
-        a.cell_len = cell_len;
+        a.cell_len = x.cell_len;
         a.stripes = stripes;
-        cs.expected = d_expected;
-        cs.bad = d_bad;
+        cs.expected = x.d_expected;
+        cs.bad = x.d_bad;
         cs.file = d_file;
         cs.file_stride = file_stride;
-        cs.n_total = uint32_t(n);
-        cs.kind = kind;
+        cs.n_total = uint32_t(x.n());
+        cs.kind = x.kind;
         cs.stripe_list = d_list;
-        const int rc = hec::launch_read_crc_rows(a, cs, lens, c->device, stream);
-        if (rc == 0) return HEC_OK;
-        if (rc > 0) return to_status(rc);
-        // -1: refused, nothing launched
+        const int rc = fused_status(hec::launch_read_crc_rows(a, cs, lens, x.c->device, x.stream));
+        if (rc != -1) return rc;  // -1: refused, nothing launched
     }
     hec::ReadRowsBytesArgs a;
     std::memset(&a, 0, sizeof(a));
+    fill_units(g.survivors.data(), k, x.shards(), unit_slots(a.in, a.in_stride, a.in_id));
     size_t data_in = 0;
-    for (size_t i = 0; i < k; i++) {
-        const size_t u = g.survivors[i];
-        a.in[i] = d_shards[u];
-        a.in_stride[i] = shard_strides[u];
-        a.in_id[i] = uint8_t(u);
-        data_in += u < k;
-    }
+    for (size_t i = 0; i < k; i++) data_in += g.survivors[i] < k;
     a.k = int32_t(k);
-    a.n_total = uint32_t(n);
+    a.n_total = uint32_t(x.n());
     a.file = d_file;
     a.file_stride = file_stride;
-    a.expected = d_expected;
-    a.bad = d_bad;
-    a.kind = kind;
+    a.expected = x.d_expected;
+    a.bad = x.d_bad;
+    a.kind = x.kind;
     a.stripe_list = d_list;
     a.stripes = stripes;
     a.lens = lens;
-    a.cell_len = cell_len;
-    a.bytes_per_checksum = bpc;
-    a.parity_in = d_expected ? int32_t(k - data_in) : 0;
-    for (size_t j0 = 0; j0 == 0 || j0 < e; j0 += size_t(hec::kMaxR)) {
-        const size_t rn = std::min(size_t(hec::kMaxR), e - j0);
-        std::memset(a.coef, 0, sizeof(a.coef));
-        std::memset(a.role, hec::kReadRowsSkip, sizeof(a.role));
-        for (size_t i = 0; j0 == 0 && i < data_in; i++) a.role[g.survivors[i]] = uint8_t(i);
-        for (size_t j = 0; j < rn; j++) {
-            a.role[g.lost[j0 + j]] = uint8_t(hec::kReadRowsLost | j);
-            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = g.plan->matrix[(j0 + j) * k + i];
-        }
-        a.r = int32_t(rn);
-        const int rc = hec::launch_read_rows_bytes(a, c->device, stream);
-        if (rc != 0) return rc < 0 ? HEC_ERR_INVALID_ARG : to_status(rc);
-        a.expected = nullptr;  // the survivors are verified once
-        a.bad = nullptr;
-        a.parity_in = 0;
-    }
-    return HEC_OK;
+    a.cell_len = x.cell_len;
+    a.bytes_per_checksum = x.bpc;
+    a.parity_in = x.d_expected ? int32_t(k - data_in) : 0;
+    return byte_route_rows(
+        e, true,
+        [&](size_t j0, size_t rn) {
+            std::memset(a.coef, 0, sizeof(a.coef));
+            std::memset(a.role, hec::kReadRowsSkip, sizeof(a.role));
+            for (size_t i = 0; j0 == 0 && i < data_in; i++) a.role[g.survivors[i]] = uint8_t(i);
+            for (size_t j = 0; j < rn; j++) {
+                a.role[g.lost[j0 + j]] = uint8_t(hec::kReadRowsLost | j);
+                for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = g.plan->matrix[(j0 + j) * k + i];
+            }
+            a.r = int32_t(rn);
+            if (j0 != 0) {  // the survivors are verified once
+                a.expected = nullptr;
+                a.bad = nullptr;
+                a.parity_in = 0;
+            }
+        },
+        [&] { return hec::launch_read_rows_bytes(a, x.c->device, x.stream); });
 }
+
 
 }  // namespace
 
@@ -4423,17 +4328,17 @@ int hec_read_crc_rows_device(hec_coder_t* c, int checksum_type, const uint8_t* c
         if (rc != HEC_OK) return rc;
         DeviceGuard dg(c->device);
         if (!dg.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
         const uint64_t full = uint64_t(c->k) * cell_len;
         const size_t stride = file_stride ? file_stride : size_t(full);
         // one launch over the stripes - 1 full stripes and one over the last,
         // or one over all of them when the last is full too
         const size_t n_full = geo.last_len == full ? stripes : stripes - 1;
-        rc = read_rows_launch(c, kind, g, nullptr, n_full, hec::ReconRowsLens{nullptr, full, 0}, d_shards, shard_strides,
-                              d_file, stride, cell_len, bytes_per_checksum, d_expected, d_bad, stream);
+        rc = read_rows_launch(x, g, nullptr, n_full, hec::ReconRowsLens{nullptr, full, 0}, d_file, stride);
         if (rc != HEC_OK || n_full == stripes) return rc;
-        return read_rows_launch(c, kind, g, nullptr, 1, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, d_shards,
-                                shard_strides, d_file, stride, cell_len, bytes_per_checksum, d_expected, d_bad, stream);
+        return read_rows_launch(x, g, nullptr, 1, hec::ReconRowsLens{nullptr, geo.last_len, stripes - 1}, d_file,
+                                stride);
     });
 }
 
@@ -4472,19 +4377,19 @@ int hec_read_crc_rows_device_mixed(hec_coder_t* c, int checksum_type, const uint
                 if (!d_shards[u]) return HEC_ERR_INVALID_ARG;  // a survivor needs storage
         DeviceGuard dg(c->device);
         if (!dg.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
-        const hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+        const VerifiedCall x{c, kind, d_shards, shard_strides, nullptr, nullptr, cell_len, bytes_per_checksum,
+                             d_expected, d_bad, nullptr, static_cast<hipStream_t>(hip_stream)};
         // 2. the lists and lengths, one copy
         uint8_t* ws = static_cast<uint8_t*>(d_workspace);
-        rc = upload_pinned(c, w.need, ws, stream, [&](uint8_t* host) { write_read_rows_image(host, plan, w); });
+        rc = upload_pinned(c, w.need, ws, x.stream, [&](uint8_t* host) { write_read_rows_image(host, plan, w); });
         if (rc != HEC_OK) return rc;
         // 3. one launch per mask over its stripes, full and short together
         const uint32_t* d_list = reinterpret_cast<const uint32_t*>(ws);
         const uint64_t* d_bytes = reinterpret_cast<const uint64_t*>(ws + w.bytes_pos);
         const size_t stride = file_stride ? file_stride : c->k * cell_len;
         for (const ReadRowsGroup& g : plan.groups) {
-            rc = read_rows_launch(c, kind, g, d_list + g.first, g.count, hec::ReconRowsLens{d_bytes + g.first, 0, 0},
-                                  d_shards, shard_strides, d_file, stride, cell_len, bytes_per_checksum, d_expected,
-                                  d_bad, stream);
+            rc = read_rows_launch(x, g, d_list + g.first, g.count, hec::ReconRowsLens{d_bytes + g.first, 0, 0}, d_file,
+                                  stride);
             if (rc != HEC_OK) return rc;
         }
         return HEC_OK;
