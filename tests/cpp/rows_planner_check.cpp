@@ -185,6 +185,65 @@ void check_shape(size_t k, size_t m) {
     hec_coder_destroy(c);
 }
 
+// Every set of at most m lost units of RS(k,m), by size and then in lexical
+// order (1471 for RS(10,4)), with the lengths of the GPU pattern tests' batch
+// cut in unit k - 1 (tests/rows_shape_cases.py: the cut unit holds x bytes, x
+// by rotation over X(cell_len); x == cell_len is a full stripe); behind them
+// the same masks once more as full stripes.  Every pattern with a lost unit is
+// a plan of its own, and all but those of x == cell_len have a full and a
+// short list.
+void pattern_batch(size_t k, size_t m, size_t cell_len, std::vector<uint64_t>* present, std::vector<uint64_t>* bytes) {
+    const size_t n = k + m;
+    const uint64_t all = (uint64_t(1) << n) - 1;
+    std::vector<uint64_t> xs;
+    for (uint64_t x : {uint64_t(1), uint64_t(15), uint64_t(16), uint64_t(17), uint64_t(511), uint64_t(512), uint64_t(513),
+                       uint64_t(1040), uint64_t(4097), uint64_t(4625), uint64_t(8193), uint64_t(8721),
+                       uint64_t(cell_len - 16), uint64_t(cell_len - 1), uint64_t(cell_len)})
+        if (x >= 1 && x <= cell_len && std::find(xs.begin(), xs.end(), x) == xs.end()) xs.push_back(x);
+    std::sort(xs.begin(), xs.end());
+    std::vector<uint64_t> masks;
+    for (size_t size = 0; size <= m; size++) {
+        std::vector<size_t> idx(size);
+        for (size_t i = 0; i < size; i++) idx[i] = i;
+        for (;;) {
+            uint64_t lost = 0;
+            for (size_t u : idx) lost |= uint64_t(1) << u;
+            masks.push_back(all & ~lost);
+            size_t i = size;
+            while (i > 0 && idx[i - 1] == n - size + (i - 1)) i--;
+            if (i == 0) break;
+            idx[i - 1]++;
+            for (size_t j = i; j < size; j++) idx[j] = idx[j - 1] + 1;
+        }
+    }
+    present->clear();
+    bytes->clear();
+    for (size_t i = 0; i < masks.size(); i++) {
+        present->push_back(masks[i]);
+        bytes->push_back(uint64_t(k - 1) * cell_len + xs[i % xs.size()]);
+    }
+    for (uint64_t mask : masks) {
+        present->push_back(mask);
+        bytes->push_back(0);
+    }
+}
+
+void check_patterns() {
+    hec_coder_t* c = nullptr;
+    if (hec_coder_create(10, 4, HEC_DEVICE_HOST, &c) != HEC_OK || !c) die("hec_coder_create(10, 4)");
+    std::vector<uint64_t> present, bytes;
+    pattern_batch(10, 4, 5136, &present, &bytes);
+    if (present.size() != 2 * 1471) die("RS(10,4) has %zu patterns, not 1471", present.size() / 2);
+    const size_t short_before = g_short, full_before = g_full;
+    check_batch(c, present, {}, true, bytes, false, 5136, "RS(10,4) every pattern");
+    // 1470 plans (pattern 0 loses nothing: no target); x == cell_len at patterns 12, 25, ...
+    size_t full_cuts = 0;
+    for (size_t i = 1; i < 1471; i++) full_cuts += bytes[i] == uint64_t(10) * 5136;
+    if (full_cuts != 113 || g_short - short_before != 1470 - full_cuts || g_full - full_before != 1470 + full_cuts)
+        die("every pattern: %zu short and %zu full entries", g_short - short_before, g_full - full_before);
+    hec_coder_destroy(c);
+}
+
 }  // namespace
 
 int main() {
@@ -192,6 +251,7 @@ int main() {
     check_shape(6, 3);
     check_shape(10, 4);
     check_shape(12, 6);
+    check_patterns();
     std::printf("rows_planner_check: ok, %zu batches, %zu full and %zu short list entries\n", g_batches, g_full, g_short);
     return 0;
 }

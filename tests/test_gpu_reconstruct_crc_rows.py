@@ -85,6 +85,14 @@ def stripes_sums(k, m, cell, rs, bpc, ctype, seed=0):
     return _sums[key]
 
 
+def forget_truth(k, m, cell, rs):
+    """Drops what stripes_truth and stripes_sums keep of one batch (a large
+    batch holds over 100 MB)."""
+    for cache in (_cells, _sums):
+        for key in [key for key in cache if key[:4] == (k, m, cell, tuple(rs))]:
+            del cache[key]
+
+
 class Case:
     """One call's buffers and their expected images.
 

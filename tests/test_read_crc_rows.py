@@ -178,4 +178,5 @@ def test_planner_under_address_and_ub_sanitizer():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     r = subprocess.run([os.path.join(PKG_DIR, target)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "read_rows_planner_check: ok, 96 batches" in r.stdout, r.stdout[-2000:]
+    # 96 sampled batches and the one of all 1471 RS(10,4) loss patterns
+    assert "read_rows_planner_check: ok, 97 batches" in r.stdout, r.stdout[-2000:]
