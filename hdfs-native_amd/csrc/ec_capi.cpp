@@ -1653,6 +1653,69 @@ int hec_scrub_device(hec_coder_t* c, const uint8_t* const* d_shards, const size_
     });
 }
 
+// ---- scrub correction: fix the located unit in place -------------------------
+
+int hec_scrub_correct(hec_coder_t* c, uint8_t* const* shards, size_t shard_len, hec_scrub_result_t* out, int* unit) {
+    if (!c || !shards || shard_len == 0 || !unit) return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!shards[i]) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        // always the host routine, as hec_scrub
+        hec_scrub_result_t r{};
+        *unit = hec::host::scrub_correct(hec::host::best_isa(), c->enc.data() + c->k * c->k, c->enc_aff.data(), c->k,
+                                         c->m, shards, shard_len, &r.ruled_out, &r.bad_bytes);
+        if (out) *out = r;
+        return int(HEC_OK);
+    });
+}
+
+int hec_scrub_correct_device(hec_coder_t* c, uint8_t* const* d_shards, const size_t* shard_strides, size_t cell_len,
+                             size_t stripes, const hec_scrub_result_t* d_results, int32_t* d_units,
+                             void* hip_stream) {
+    if (c && c->device == HEC_DEVICE_HOST) return host_only("hec_scrub_correct_device");
+    if (!c || !d_shards || !shard_strides || cell_len == 0 || !d_results || !d_units ||
+        (reinterpret_cast<uintptr_t>(d_results) & 7u) != 0 || (reinterpret_cast<uintptr_t>(d_units) & 3u) != 0)
+        return HEC_ERR_INVALID_ARG;
+    for (size_t i = 0; i < c->k + c->m; i++)
+        if (!d_shards[i]) return HEC_ERR_INVALID_ARG;
+    if (stripes == 0) return HEC_OK;
+    if (stripes > SIZE_MAX / sizeof(hec_scrub_result_t)) return HEC_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t k = c->k, m = c->m;
+        hec::ScrubCorrectArgs a;
+        std::memset(&a, 0, sizeof(a));
+        for (size_t i = 0; i < k + m; i++) {
+            a.base[i] = d_shards[i];
+            a.stride[i] = shard_strides[i];
+        }
+        const uint8_t* P = c->enc.data() + k * k;
+        for (size_t j = 0; j < m; j++)
+            for (size_t i = 0; i < k; i++) a.coef[j * hec::kMaxK + i] = P[j * k + i];
+        // unit t's error is scale[t] * s_row[t]: the first row that sees a data
+        // unit (a zero column of P: scale 0, nothing is added), its own row
+        // for a parity unit
+        for (size_t t = 0; t < k; t++) {
+            size_t j = 0;
+            while (j < m && P[j * k + t] == 0) j++;
+            a.row[t] = uint8_t(j < m ? j : 0);
+            a.scale[t] = j < m ? hec::gf_inv(P[j * k + t]) : uint8_t(0);
+        }
+        for (size_t j = 0; j < m; j++) {
+            a.row[k + j] = uint8_t(j);
+            a.scale[k + j] = 1;
+        }
+        a.k = int32_t(k);
+        a.m = int32_t(m);
+        a.cell_len = cell_len;
+        a.stripes = stripes;
+        a.results = reinterpret_cast<const uint64_t*>(d_results);
+        a.units = d_units;
+        DeviceGuard g(c->device);
+        if (!g.ok) return fail(HEC_ERR_DEVICE, "hipSetDevice", hipErrorInvalidDevice);
+        return to_status(hec::launch_scrub_correct(a, c->device, static_cast<hipStream_t>(hip_stream)));
+    });
+}
+
 // ---- degraded scrub: one presence mask per stripe ---------------------------
 
 int hec_scrub_plan(const char* codec, size_t data_units, size_t parity_units, const uint8_t* present, size_t* n_checks,

@@ -190,6 +190,33 @@ struct ScrubArgs {
 // must already be zeroed in stream order.  0 ok, -1 invalid sizes, >0 hipError_t.
 int launch_scrub(const ScrubArgs& a, int device, hipStream_t stream);
 
+// ---- scrub correction: fix the located unit in place -------------------------
+// Argument block of gf_scrub_correct / gf_scrub_correct_bytes
+// (ec_scrub_correct.hip).  Reads `results` (what a scrub of these very cells
+// wrote, earlier on the stream), writes `units` for every stripe and, in a
+// LOCATED stripe, the located unit's cell; everything else is read-only.
+constexpr int32_t kCorrectClean = -1;      // HEC_CORRECT_CLEAN
+constexpr int32_t kCorrectUnlocated = -2;  // HEC_CORRECT_UNLOCATED
+struct ScrubCorrectArgs {
+    uint8_t* base[kMaxShards];        // all k+m unit bases, none null
+    uint64_t stride[kMaxShards];
+    uint8_t coef[16 * kMaxK];         // parity block P: row j, column i at [j*kMaxK + i]
+    uint8_t row[kMaxShards];          // unit t: the syndrome row its error is read from, < m
+    uint8_t scale[kMaxShards];        // unit t: 1 / H[row[t]][t]
+    int32_t k, m;
+    uint64_t cell_len;
+    uint64_t stripes;
+    const uint64_t* results;          // [stripes][2], 8-B aligned
+    int32_t* units;                   // [stripes]: the located unit, kCorrectClean or kCorrectUnlocated
+    uint32_t chunks, tiles_per_stripe, total_tiles;  // register kernel (the launcher fills them)
+};
+
+// Corrects a batch.  The register kernel takes k in {2,3,6,10}, m <= 4 and
+// 16-B aligned bases, strides and cell_len; everything else runs the
+// byte-granular kernel (same results).  One kernel launch, no counters, no
+// workspace.  0 ok, -1 invalid sizes, >0 hipError_t.
+int launch_scrub_correct(const ScrubCorrectArgs& a, int device, hipStream_t stream);
+
 // ---- degraded scrub: one presence mask per stripe ---------------------------
 // Plan blob entry of gf_scrub_mixed / gf_scrub_mixed_bytes (ec_scrub_mixed.hip):
 // the stripe's survivors S (first k present units), extras E (the other

@@ -226,6 +226,39 @@ class Coder {
     }
     ScrubResult scrub_result(const hec_scrub_result_t& r) const { return make_result(r); }
 
+    // Scrub correction (hec_scrub_correct): scrubs the stripe and, where one
+    // unit is LOCATED, fixes it in place (units[t] ^= the error the syndromes
+    // give).  Returns the pair the scrub found; *unit (if not null) receives
+    // the corrected unit, HEC_CORRECT_CLEAN or HEC_CORRECT_UNLOCATED (nothing
+    // written).  Host routine.
+    ScrubResult scrub_correct(std::vector<Bytes>& units, int* unit = nullptr) const {
+        if (units.size() != k_ + m_) throw std::invalid_argument("scrub_correct: need data_units + parity_units units");
+        const size_t n = units[0].size();
+        std::vector<uint8_t*> io(units.size());
+        for (size_t i = 0; i < units.size(); i++) {
+            if (units[i].size() != n) throw std::invalid_argument("scrub_correct: units of unequal length");
+            io[i] = units[i].data();
+        }
+        hec_scrub_result_t r{};
+        int u = 0;
+        check(hec_scrub_correct(h_.get(), io.data(), n, &r, &u));
+        if (unit) *unit = u;
+        return make_result(r);
+    }
+    // Device-resident batch, asynchronous on hip_stream: d_results is what
+    // scrub_device / scrub_crc_device wrote for these cells earlier on the
+    // stream; d_units[stripes] (int32, device memory) receives every stripe's
+    // corrected unit, HEC_CORRECT_CLEAN or HEC_CORRECT_UNLOCATED.  One kernel,
+    // no workspace.
+    void scrub_correct_device(const std::vector<uint8_t*>& d_units_io, const std::vector<size_t>& strides,
+                              size_t cell_len, size_t stripes, const hec_scrub_result_t* d_results, int32_t* d_units,
+                              void* hip_stream = nullptr) const {
+        if (d_units_io.size() != k_ + m_ || strides.size() != k_ + m_)
+            throw std::invalid_argument("scrub_correct_device: need data_units + parity_units units");
+        check(hec_scrub_correct_device(h_.get(), d_units_io.data(), strides.data(), cell_len, stripes, d_results,
+                                       d_units, hip_stream));
+    }
+
     // Degraded scrub (hec_scrub_degraded): a stripe with missing units,
     // nullopt = missing.  The missing units' bits are set in ruled_out once a
     // position is bad; k units present or fewer cannot be checked: (0, 0).

@@ -405,5 +405,49 @@ void scrub(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, c
     *bad_bytes = bad;
 }
 
+int scrub_correct(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, uint8_t* const* units, size_t n,
+                  uint64_t* ruled_out, uint64_t* bad_bytes) {
+    scrub(isa, P, aff, k, m, units, n, ruled_out, bad_bytes);
+    if (*bad_bytes == 0) return -1;
+    // hec_scrub_verdict: LOCATED iff exactly one unit is not ruled out
+    const uint64_t all = k + m == 64 ? ~uint64_t(0) : (uint64_t(1) << (k + m)) - 1;
+    const uint64_t cand = ~*ruled_out & all;
+    if (cand == 0 || (cand & (cand - 1)) != 0) return -2;
+    const size_t t = size_t(__builtin_ctzll(cand));
+    // the row the error is read from and 1 / H[row][t]
+    size_t row = 0;
+    uint8_t scale = 1;
+    if (t < k) {
+        while (row < m && P[row * k + t] == 0) row++;
+        if (row == m) return int(t);  // a zero column of P: no row sees the unit, nothing to add
+        scale = gf_inv(P[row * k + t]);
+    } else {
+        row = t - k;
+    }
+    const size_t block = std::min(n, scrub_block_bytes());
+    std::vector<uint8_t> scratch(2 * block);
+    uint8_t* const syn = scratch.data();
+    uint8_t* const err = scratch.data() + block;
+    const uint8_t* in[64];
+    for (size_t o = 0; o < n; o += block) {
+        const size_t len = std::min(block, n - o);
+        for (size_t i = 0; i < k; i++) in[i] = units[i] + o;
+        uint8_t* out = syn;
+        gf_matmul(isa, P + row * k, aff ? aff + row * k : nullptr, 1, k, in, &out, len);
+        const uint8_t* par = units[k + row] + o;
+        for (size_t b = 0; b < len; b++) syn[b] ^= par[b];
+        const uint8_t* e = syn;
+        if (scale != 1) {
+            const uint8_t* sin = syn;
+            out = err;
+            gf_matmul(isa, &scale, nullptr, 1, 1, &sin, &out, len);
+            e = err;
+        }
+        uint8_t* dst = units[t] + o;
+        for (size_t b = 0; b < len; b++) dst[b] ^= e[b];
+    }
+    return int(t);
+}
+
 }  // namespace host
 }  // namespace hec

@@ -77,5 +77,17 @@ void scrub(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, c
            uint64_t* ruled_out, uint64_t* bad_bytes);
 size_t scrub_block_bytes();
 
+// Scrub correction on the host (hec_scrub_correct): scrub() as above, then the
+// verdict of hec_scrub_verdict over k + m units.  Returns -1 for a clean
+// stripe and -2 for one that is not LOCATED (nothing written); for a LOCATED
+// unit t, returns t after units[t][b] ^= scale * s_row(b) for every b < n,
+// with row the first j with P[j][t] != 0 and scale = 1 / P[j][t] for a data
+// unit, row = t - k and scale = 1 for a parity unit.  The one syndrome row is
+// computed by gf_matmul in blocks of scrub_block_bytes() into a scratch of
+// two such blocks: nothing grows with n.  *ruled_out / *bad_bytes receive the
+// pair scrub() found (before the correction).
+int scrub_correct(Isa isa, const uint8_t* P, const uint64_t* aff, size_t k, size_t m, uint8_t* const* units, size_t n,
+                  uint64_t* ruled_out, uint64_t* bad_bytes);
+
 }  // namespace host
 }  // namespace hec

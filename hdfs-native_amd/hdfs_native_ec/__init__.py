@@ -38,6 +38,10 @@ HEC_SCRUB_LOCATED = 1
 HEC_SCRUB_AMBIGUOUS = 2
 HEC_SCRUB_MULTIPLE = 3
 
+# hec_scrub_correct[_device]: the unit values that are not a unit index
+CORRECT_CLEAN = -1      # HEC_CORRECT_CLEAN: bad_bytes == 0, stripe untouched
+CORRECT_UNLOCATED = -2  # HEC_CORRECT_UNLOCATED: AMBIGUOUS or MULTIPLE, stripe untouched
+
 # ChecksumTypeProto values (rust/src/proto/hadoop.hdfs.rs:1363)
 CHECKSUM_NULL = 0
 CHECKSUM_CRC32 = 1   # crc CRC_32_CKSUM (connection.rs:37)
@@ -68,7 +72,7 @@ EXPORTS = [
     "hec_reconstruct_sums_device", "hec_reconstruct_sums_device_mixed",
     "hec_reconstruct_crc_rows_device", "hec_reconstruct_crc_rows_mixed_workspace_size",
     "hec_reconstruct_crc_rows_device_mixed",
-    "hec_scrub_verdict", "hec_scrub", "hec_scrub_device",
+    "hec_scrub_verdict", "hec_scrub", "hec_scrub_device", "hec_scrub_correct", "hec_scrub_correct_device",
     "hec_scrub_plan", "hec_scrub_degraded", "hec_scrub_mixed_workspace_size", "hec_scrub_device_mixed",
     "hec_scrub_crc_device", "hec_scrub_crc_mixed_workspace_size", "hec_scrub_crc_device_mixed",
     "hec_scrub_crc_rows_device", "hec_scrub_crc_rows_mixed_workspace_size", "hec_scrub_crc_rows_device_mixed",
@@ -208,6 +212,8 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hec_scrub_verdict": ([ctypes.c_uint64, ctypes.c_uint64, S, ctypes.POINTER(I)], I),
         "hec_scrub": ([P, PP, S, P], I),
         "hec_scrub_device": ([P, PP, SP, S, S, P, P], I),
+        "hec_scrub_correct": ([P, PP, S, P, ctypes.POINTER(I)], I),
+        "hec_scrub_correct_device": ([P, PP, SP, S, S, P, P, P], I),
         "hec_scrub_plan": ([ctypes.c_char_p, S, S, P, SP, SP, SP, P], I),
         "hec_scrub_degraded": ([P, PP, S, P], I),
         "hec_scrub_mixed_workspace_size": ([P, S], S),
@@ -639,6 +645,35 @@ class Coder:
         memory for `stripes` pairs of uint64 (ruled_out, bad_bytes), zeroed by the call."""
         _check(self._lib.hec_scrub_device(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides), cell_len,
                                           stripes, ctypes.c_void_p(results_ptr), ctypes.c_void_p(stream)))
+
+    def scrub_correct(self, shards):
+        """hec_scrub_correct: scrub one stripe of k+m writable buffers
+        (bytearray, writable numpy uint8 arrays, ...) and, where one unit is
+        LOCATED, fix it in place.  -> (ruled_out, bad_bytes, unit): the pair the
+        scrub found and the corrected unit, CORRECT_CLEAN or CORRECT_UNLOCATED
+        (nothing written).  Host routine."""
+        import numpy as np
+        n_units = self.data_units + self.parity_units
+        assert len(shards) == n_units
+        views = [np.frombuffer(d, dtype=np.uint8) for d in shards]
+        n = len(views[0])
+        assert all(len(v) == n for v in views), "equal shard lengths"
+        assert all(v.flags.writeable for v in views), "writable buffers"
+        res = (ctypes.c_uint64 * 2)()
+        unit = ctypes.c_int(0)
+        _check(self._lib.hec_scrub_correct(self._h, _pp([v.ctypes.data for v in views]), n, res, ctypes.byref(unit)))
+        return int(res[0]), int(res[1]), unit.value
+
+    def scrub_correct_device(self, shard_ptrs, shard_strides, cell_len, stripes, results_ptr, units_ptr,
+                             stream: int = 0) -> None:
+        """hec_scrub_correct_device: shard_ptrs[k+m] (none missing, writable);
+        results_ptr = what scrub_device / scrub_crc_device wrote for these
+        cells earlier on the stream; units_ptr = device memory for `stripes`
+        int32 (the corrected unit, CORRECT_CLEAN or CORRECT_UNLOCATED),
+        written for every stripe."""
+        _check(self._lib.hec_scrub_correct_device(self._h, _pp([p or 0 for p in shard_ptrs]), _sp(shard_strides),
+                                                  cell_len, stripes, ctypes.c_void_p(results_ptr),
+                                                  ctypes.c_void_p(units_ptr), ctypes.c_void_p(stream)))
 
     def scrub_degraded(self, shards: Sequence[Optional[bytes]]):
         """hec_scrub_degraded: (ruled_out, bad_bytes) of one stripe, None =
@@ -1399,6 +1434,26 @@ def scrub_batch(coder: Coder, cells, stream=None):
     ptrs, strides = stripe_layout_ptrs(cells, n)
     coder.scrub_device(ptrs, strides, cells.shape[2], S, out.data_ptr(), s.cuda_stream)
     return out
+
+
+def scrub_correct_batch(coder: Coder, cells, results, units=None, stream=None):
+    """Fix, in place, the unit that a scrub located in each stripe of cells
+    (uint8 cuda tensor [S, k+m, cell]): results is the int64 [S, 2] tensor
+    scrub_batch or scrub_crc_batch returned for these very cells on the same
+    stream, with no write to cells in between.  -> int32 cuda tensor [S]: the
+    corrected unit, CORRECT_CLEAN or CORRECT_UNLOCATED (stripe untouched).
+    Pass `units` to write into a tensor of your own.  One kernel, no workspace;
+    asynchronous on the stream."""
+    import torch
+    n = coder.data_units + coder.parity_units
+    S = cells.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(cells.device)
+    if units is None:
+        with torch.cuda.stream(s):
+            units = torch.empty((S,), dtype=torch.int32, device=cells.device)
+    ptrs, strides = stripe_layout_ptrs(cells, n)
+    coder.scrub_correct_device(ptrs, strides, cells.shape[2], S, results.data_ptr(), units.data_ptr(), s.cuda_stream)
+    return units
 
 
 def scrub_batch_mixed(coder: Coder, cells, present_masks: Sequence[int], stream=None, workspace=None):

@@ -583,6 +583,73 @@ int hec_scrub(hec_coder_t *coder, const uint8_t *const *shards, size_t shard_len
 int hec_scrub_device(hec_coder_t *coder, const uint8_t *const *d_shards, const size_t *shard_strides,
                      size_t cell_len, size_t stripes, hec_scrub_result_t *d_results, void *hip_stream);
 
+/* Scrub correction: fix the unit a scrub LOCATED, in place, from the scrub's
+ * own result -- no inverse, no plan, no workspace, no host round trip.  One
+ * corrupt unit t with error e(b) leaves s_j(b) = H[j][t] * e(b) in every row,
+ * so the error is one syndrome divided by one constant:
+ *   e(b) = scale[t] * s_row[t](b),
+ *   data unit t:     row[t] = the first j with P[j][t] != 0, scale[t] = 1 / P[j][t];
+ *   parity unit k+j0: row = j0, scale = 1 (the cell is overwritten by row j0
+ *                     of the encode).
+ * The verdict is formed exactly as hec_scrub_verdict(ruled_out, bad_bytes,
+ * k+m, &t) does: cand = ~ruled_out & ((1 << (k+m)) - 1); the stripe is LOCATED
+ * iff bad_bytes != 0 and popcount(cand) == 1, and then t = ctz(cand).
+ *   CLEAN (bad_bytes == 0):   unit = HEC_CORRECT_CLEAN; no cell is read or written;
+ *   AMBIGUOUS or MULTIPLE (always so for m == 1):
+ *                             unit = HEC_CORRECT_UNLOCATED; nothing is written;
+ *   LOCATED unit t:           unit = t and u_t(b) ^= e(b) for every b < cell_len.
+ * Only unit t's cell is written: bytes of it with e(b) == 0 keep their value
+ * (whether or not they are stored again), no byte outside [0, cell_len) of
+ * that cell changes, the other units are read-only.  One corrupt unit, with
+ * m >= 2, comes back bit-exact.  What the verdict proves carries over from
+ * hec_scrub_verdict word for word: with m >= 3, LOCATED is exact for up to m-1
+ * corrupt units; with m == 2, LOCATED assumes at most one corrupt unit (two
+ * corrupt units that pass for one are "corrected" to a consistent but wrong
+ * stripe; chunk sums, hec_scrub_crc_device, tell).
+ *
+ * Out of scope: a _mixed form for degraded stripes (a stripe with missing
+ * units goes through hec_reconstruct_device_mixed); a form that understands
+ * the stripe lengths of the _rows scrubs; chunk sums -- the call does not
+ * touch them: a unit whose bytes were wrong and whose sums were right verifies
+ * again after the fix, which a second hec_scrub_crc_device shows.
+ *
+ * hec_scrub_correct (host, synchronous): runs the host routine of hec_scrub
+ * over shards[k+m] (writable host buffers of shard_len bytes, none NULL),
+ * stores the pair it found in *out if out is not NULL, and on LOCATED corrects
+ * in place.  *unit receives t, HEC_CORRECT_CLEAN or HEC_CORRECT_UNLOCATED.
+ * Always the host routine, also on host-only coders; no allocation grows with
+ * shard_len.  HEC_ERR_INVALID_ARG for a NULL coder, shards, shard or unit, or
+ * shard_len == 0.
+ *
+ * hec_scrub_correct_device (asynchronous on hip_stream), units laid out as for
+ * hec_scrub_device.  The caller's contract: d_results[stripes] is what
+ * hec_scrub_device or hec_scrub_crc_device wrote for these very cells (same
+ * d_shards, strides, cell_len and stripes), earlier on the same stream, with
+ * no write to the cells in between.  d_results is read on the device and is
+ * read-only; d_units[stripes] (device memory, 4-byte aligned) is written for
+ * every stripe by the call itself (no memset is queued; the caller need not
+ * initialise it).  The call reads the k data cells and one parity cell of the
+ * LOCATED stripes only.  It does not synchronise, does not allocate, takes no
+ * workspace and leases no queue counters; under stream capture it is one kernel
+ * node, so scrub -> correct -> scrub runs on one stream or in one graph with
+ * one read-back of d_units and the final results ("Scrub,
+ * correct, scrub"; stripes left at HEC_CORRECT_UNLOCATED go through the
+ * reconstruct loop).  k in {2,3,6,10} with m <= 4 and 16-B aligned bases,
+ * strides and cell_len run the register kernel; other shapes a byte-granular
+ * kernel with the same results.  stripes == 0 -> HEC_OK, nothing queued.
+ * HEC_ERR_INVALID_ARG (nothing queued) for a NULL coder, d_shards,
+ * shard_strides, d_results or d_units, a NULL d_shards[i], cell_len == 0,
+ * d_results not 8-byte aligned or d_units not 4-byte aligned; HEC_ERR_DEVICE
+ * on a host-only coder. */
+#define HEC_CORRECT_CLEAN (-1)     /* bad_bytes == 0: stripe untouched */
+#define HEC_CORRECT_UNLOCATED (-2) /* AMBIGUOUS or MULTIPLE: stripe untouched */
+
+int hec_scrub_correct(hec_coder_t *coder, uint8_t *const *shards, size_t shard_len,
+                      hec_scrub_result_t *out /* may be NULL */, int *unit);
+int hec_scrub_correct_device(hec_coder_t *coder, uint8_t *const *d_shards, const size_t *shard_strides,
+                             size_t cell_len, size_t stripes, const hec_scrub_result_t *d_results,
+                             int32_t *d_units, void *hip_stream);
+
 /* Degraded scrub: a stripe with missing units.  Of its p present units, S is
  * the first k in ascending order (the survivors every reconstruction call
  * picks), E the other e = p - k (the extras, ascending), 0 <= e <= m.  With

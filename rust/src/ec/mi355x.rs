@@ -139,6 +139,9 @@ unsafe extern "C" {
     fn hec_scrub(c: *mut HecCoder, shards: *const *const u8, shard_len: usize, out: *mut ScrubResult) -> c_int;
     fn hec_scrub_device(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize, cell_len: usize,
                         stripes: usize, d_results: *mut ScrubResult, stream: *mut c_void) -> c_int;
+    fn hec_scrub_correct_device(c: *mut HecCoder, d_shards: *const *mut u8, shard_strides: *const usize,
+                                cell_len: usize, stripes: usize, d_results: *const ScrubResult, d_units: *mut i32,
+                                stream: *mut c_void) -> c_int;
     fn hec_scrub_mixed_workspace_size(c: *const HecCoder, stripes: usize) -> usize;
     fn hec_scrub_device_mixed(c: *mut HecCoder, d_shards: *const *const u8, shard_strides: *const usize,
                               present: *const u64, cell_len: usize, stripes: usize, d_results: *mut ScrubResult,
@@ -606,6 +609,30 @@ impl GpuCoder {
         assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
         check(unsafe {
             hec_scrub_device(self.raw, shards.as_ptr(), shard_strides.as_ptr(), cell, stripes, results, stream)
+        })
+    }
+
+    /// Fixes, in place, the unit a scrub located (`hec_scrub_correct_device`):
+    /// `results` is what `scrub_device` or `scrub_crc_device` wrote for these
+    /// very cells earlier on `stream`, with no write to them in between.  Per
+    /// stripe the verdict of `scrub_verdict` is formed on the device;
+    /// `units[s]` (device memory, `stripes` x `i32`, written for every stripe)
+    /// receives the corrected unit, -1 (`HEC_CORRECT_CLEAN`) or -2
+    /// (`HEC_CORRECT_UNLOCATED`, stripe untouched: repair it with `reconstruct_device_mixed`).  One
+    /// kernel, no workspace, no synchronisation: scrub, correct, scrub run on
+    /// one stream or in one captured graph.
+    ///
+    /// # Safety
+    /// As `scrub_device`, with every `shards[i]` writable; `units` valid for
+    /// `stripes * 4` bytes on this device.
+    pub unsafe fn scrub_correct_device(&self, shards: &[*mut u8], shard_strides: &[usize], cell: usize,
+                                       stripes: usize, results: *const ScrubResult, units: *mut i32,
+                                       stream: *mut c_void) -> Result<()> {
+        let n = self.data_units + self.parity_units;
+        assert!(shards.len() == n && shard_strides.len() == n, "one slot per unit");
+        check(unsafe {
+            hec_scrub_correct_device(self.raw, shards.as_ptr(), shard_strides.as_ptr(), cell, stripes, results, units,
+                                     stream)
         })
     }
 
