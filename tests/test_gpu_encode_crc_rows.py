@@ -80,6 +80,14 @@ def stripes_sums(codec, k, m, cell, rs, bpc, ctype, seed=0):
     return _sums[key]
 
 
+def forget(min_bytes):
+    """Drops the cached batches of at least min_bytes of cells, with their sums."""
+    for key in [key for key, v in _cells.items() if v[0].nbytes >= min_bytes]:
+        del _cells[key]
+        for other in [o for o in _sums if o[:5] == key[:5] and o[-1] == key[-1]]:
+            del _sums[other]
+
+
 class Enc:
     """One call's buffers and their expected images.  rs[s] = the logical bytes
     of stripe s (never 0 here).  The cell buffer is [S, k+m, cell + pad]: units

@@ -94,6 +94,14 @@ def true_sums(k, m, S, cell, codec="rs", bpc=512, ctype=C32C):
     return _sums[key]
 
 
+def forget(min_bytes):
+    """Drops the cached truths of at least min_bytes of cells, with their sums."""
+    for key in [key for key, t in _truth.items() if t.nbytes >= min_bytes]:
+        del _truth[key]
+        for other in [o for o in _sums if o[:5] == key]:
+            del _sums[other]
+
+
 def patterns(n, lo, hi):
     return [lost for e in range(lo, hi + 1) for lost in itertools.combinations(range(n), e)]
 

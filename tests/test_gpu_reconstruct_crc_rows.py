@@ -93,6 +93,12 @@ def forget_truth(k, m, cell, rs):
             del cache[key]
 
 
+def forget(min_bytes):
+    """Drops the cached batches of at least min_bytes of cells, with their sums."""
+    for key in [key for key, v in _cells.items() if v[0].nbytes >= min_bytes]:
+        forget_truth(*key[:4])
+
+
 class Case:
     """One call's buffers and their expected images.
 

@@ -77,17 +77,25 @@ def truth(codec, k, m, cell, rs, bpc, ctype):
     return _other[key]
 
 
+def forget(min_bytes):
+    """Drops the cached batches of at least min_bytes of cells."""
+    for key in [key for key, v in _other.items() if v[0].nbytes >= min_bytes]:
+        del _other[key]
+
+
 class Batch:
     """One call's buffers and the expected images.
 
     rs[s] = the logical bytes of stripe s (k * cell: full); masks[s] = the
     present units (None: all).  corrupt = [(stripe, unit, byte)]: that slot
     byte is flipped after the upload image is made, whether it lies below the
-    unit's length or not; corrupt_sums = [(stripe, unit, word)]: that expected
-    word, live or not."""
+    unit's length or not; silent = the same, and the unit's live expected sums
+    are then the oracle's of its flipped bytes (visible to the parity check
+    only); corrupt_sums = [(stripe, unit, word)]: that expected word, live or
+    not."""
 
     def __init__(self, codec, k, m, cell, rs, dev, masks=None, corrupt=(), corrupt_sums=(), bpc=512, ctype=C32C,
-                 base_off=0):
+                 base_off=0, silent=()):
         t, lens, sums = truth(codec, k, m, cell, rs, bpc, ctype)
         S, n = len(rs), k + m
         self.codec, self.k, self.m, self.n, self.S, self.cell, self.bpc, self.ctype = codec, k, m, n, S, cell, bpc, ctype
@@ -100,8 +108,11 @@ class Batch:
                 if (self.masks[s] >> u) & 1:
                     img[s, u, :lens[s][u]] = t[s, u, :lens[s][u]]
                     simg[s, u] = sums[s, u]
-        for (s, u, b) in corrupt:
+        for (s, u, b) in list(corrupt) + list(silent):
             img[s, u, b] ^= 0x40
+        for (s, u, _) in silent:
+            live = chunk_sums(img[s, u, :lens[s][u]], bpc, ctype)
+            simg[s, u, :live.shape[0]] = live
         for (s, u, c) in corrupt_sums:
             simg[s, u, c, 3] ^= 1
         self.h_cells, self.h_sums = img, simg
